@@ -9,7 +9,14 @@ HBM before the timed region. Multi-GPU: one process per GPU (torchrun), games sh
 global game id, no collective inside the timed region; the (s, pi, z) all-gather over RCCL
 runs after it and is reported separately.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds every
+side measurement to the line (rocprofv3 counter passes, the single-stream roofline leg, the
+leaf-compaction and exact-fp32 legs, the sample all-gather, the CPU baseline); the --no-* options
+then leave single ones out. --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float32 / float64, at most 64 MB in all); the inputs are seeded, so two builds run
+with the same arguments can be compared array for array.
 """
 import argparse
 import csv
@@ -76,6 +83,12 @@ def parse():
     ap.add_argument("--fp32-kernel", default="split16", choices=["split", "split16", "exact"],
                     help="fp32 NN kernel: split (bf16x6), split16 (fp16x3; both fp32-level error) or exact "
                          "(fp32 MFMA products)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (PMC passes, roofline / compaction / exact-fp32 legs, sample "
+                         "all-gather, CPU baseline); without it only the headline figure is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="cpu_baseline sample length")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -98,7 +111,46 @@ def parse():
                          "fights are tail-bound: 65 536 games 4 338 games/s, 131 072 5 112; two engines of ~70 GB)")
     ap.add_argument("--pm-playouts", type=int, default=400, help="pure_mcts mode: playouts per search")
     ap.add_argument("--train-batch", type=int, default=512, help="train mode: global batch (train.rs:142)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run measures the headline figure only
+        args.no_cpu_baseline = args.no_allgather = args.no_exact = args.no_pmc = True
+    return args
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: the most one run writes
+
+
+def dump_sample(n, most, seed=20260101):
+    """Indices of a fixed, seeded sample of at most `most` of n rows (ascending; all rows if they fit)."""
+    import numpy as np
+    if n <= most:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=most, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float32 or float64 (integers that float32 holds
+    exactly become float32, wider ones float64), within DUMP_BYTES in all."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        out[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES}-byte limit"
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in out.items():
+        np.save(d / f"{name}.npy", a)
+
+
+def state_columns(states):
+    """oaz_state records as float64 rows: kings[2], pawns[2] (25-bit boards), cards[5], to_move."""
+    import numpy as np
+    return np.concatenate([states["kings"].astype(np.float64), states["pawns"].astype(np.float64),
+                           states["cards"].astype(np.float64), states["to_move"].astype(np.float64)[:, None]], axis=1)
 
 
 def pmc_traffic(args, cfg):
@@ -626,6 +678,9 @@ def train_main(args, world, rank, local):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     T = float(tmax.item())
     v, p, k = tr.losses()
+    if rank == 0 and args.dump_outputs:  # the parameters after the last timed SGD step and the loss sums
+        dump_outputs(args.dump_outputs, {"weights": tr.get_weights(),
+                                         "loss_sums": np.array([v, p, float(k)], dtype=np.float64)})
     if rank == 0:
         fl = train_flop_per_sample(blocks) * shard
         ms = 1e3 * T / args.steps
@@ -638,6 +693,7 @@ def train_main(args, world, rank, local):
                                       f"wd 1e-4", "parallelism": f"dp{world} (RCCL all-reduce of gradients)"},
                "mean_losses": {"value": v / max(1, k), "policy": p / max(1, k)},
                "host_enqueue_ms_per_step": 1e3 * t_enq / args.steps,
+               "full": args.full,
                "roofline": {"bound": "mfma", "kernel": "whole SGD step (conv fwd/dgrad/wgrad on v_mfma_f32_16x16x4_f32)",
                             "achieved": achieved, "peak": PEAK_TFLOPS["fp32"], "unit": "TFLOP/s",
                             "frac": achieved / PEAK_TFLOPS["fp32"],
@@ -751,6 +807,11 @@ def pure_mcts_main(args, world, rank, local):
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     T = float(tmax.item())
+    if rank == 0 and args.dump_outputs and args.steps > 0:  # the last timed search: every root's move and value
+        mv = np.stack([r.moves[f] for f in ("from_", "to", "piece", "slot")], axis=1).astype(np.float32)
+        keep = dump_sample(G, DUMP_BYTES // (5 * 4))
+        dump_outputs(args.dump_outputs, {"moves": mv[keep], "values": r.values[keep],
+                                         "rows": keep.astype(np.float64)})
     if rank == 0:
         total = G * P * args.steps * world
         out = {"metric": PM_METRIC, "value": total / T, "unit": "playouts/s", "n_gpus": world, "steps": args.steps,
@@ -759,7 +820,7 @@ def pure_mcts_main(args, world, rank, local):
                "data": "synthetic (seeded 5-of-16 deals, start positions)",
                "config": {"workload": f"pure_mcts: {G} searches/GPU x {P} playouts, min_node_visits 5, c 1.41",
                           "parallelism": f"searches sharded x{world}"},
-               "searches_per_s": G * args.steps * world / T,
+               "full": args.full, "searches_per_s": G * args.steps * world / T,
                "mean_rollout_plies": plies / max(1, G * P * args.steps), "roofline": roof}
         if not args.no_cpu_baseline and world == 1:
             try:  # after the timed region: a baseline failure must not lose the measured line
@@ -828,6 +889,11 @@ def arena_main(args, world, rank, local):
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         t[0] = tm[0]
     T, plies_all, games_all = (float(x) for x in t.tolist())
+    if rank == 0 and args.dump_outputs and args.steps > 0:  # the last timed fight's statistics
+        import numpy as np
+        g = st.general
+        dump_outputs(args.dump_outputs, {"results": np.array([g.wins, g.loses, g.draws], dtype=np.float64),
+                                         "plies": np.asarray(st.plies, dtype=np.float64)})
     if rank == 0:
         out = {"metric": ARENA_METRIC, "value": games_all / T, "unit": "games/s", "n_gpus": world, "steps": args.steps,
                "warmup": 1, "ms_per_step": 1e3 * T / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -835,7 +901,7 @@ def arena_main(args, world, rank, local):
                "data": "synthetic (random-init weights seeds 0 / 1, seeded 5-of-16 deals)",
                "config": {"workload": f"arena: {n} games/GPU per fight, {sims} sims/move, 3-block, c 5, train=false, "
                                       "152-ply cut", "parallelism": f"games sharded x{world}"},
-               "sims_per_s": plies_all * sims / T, "plies_per_s": plies_all / T,
+               "full": args.full, "sims_per_s": plies_all * sims / T, "plies_per_s": plies_all / T,
                "mean_plies_per_game": plies_all / max(1.0, games_all),
                "rank0_results": {"wins": wins[0], "loses": wins[1], "draws": wins[2]},
                "note": "a fight runs until its last game ends (or the 152-ply cut), so its tail searches few games"}
@@ -853,6 +919,43 @@ def arena_main(args, world, rank, local):
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_selfplay(dirname, eng, cfg, recs, ready_before_last):
+    """--dump-outputs of the self-play bench: what the last timed ply produced.
+      samples_*   the (s, pi, z) records the ply buffered (those of the games it finished), i.e. the engine's
+                  buffered records after the first `ready_before_last`. The device appends them in the order
+                  the games' threads arrive, so they are sorted by their bytes here; a seeded sample if they
+                  would not fit.
+      tree_*      the search trees of the ply in a seeded sample of game slots: the root's children in slot
+                  order, padded to 40 (the most moves a position has): visit counts N (the ply's pi before
+                  normalisation), value sums W, priors P (with the root noise) and packed moves mv; and the
+                  tree's node count."""
+    import numpy as np
+    from onitama_az import _abi
+    if recs is None:
+        recs = eng.samples_fetch(int(eng.selfplay_stats().samples_ready))
+    last = np.ascontiguousarray(recs[ready_before_last:])
+    order = np.argsort(last.view(np.dtype((np.void, _abi.SAMPLE_DTYPE.itemsize))).reshape(-1), kind="stable")
+    last = last[order]
+    row_bytes = 10 * 8 + 50 * 4 + 4 + 8
+    last = last[dump_sample(len(last), (DUMP_BYTES // 2) // row_bytes)]
+    slots = dump_sample(cfg["games"], 512, seed=5)
+    kids = {f: np.zeros((len(slots), 40), dtype=np.float64) for f in ("N", "W", "P", "mv")}
+    nodes = np.zeros(len(slots), dtype=np.float64)
+    for i, g in enumerate(slots):
+        t = eng.tree(int(g))
+        nodes[i] = len(t)
+        if len(t):
+            a, n = int(t["first"][0]), int(t["nch"][0])
+            for f in kids:
+                kids[f][i, :n] = t[f][a:a + n]
+    dump_outputs(dirname, {"samples_state": state_columns(last["state"]), "samples_pi": last["pi"],
+                           "samples_z": last["z"],
+                           "samples_count": np.array([len(recs) - ready_before_last], np.float64),
+                           "tree_slots": slots.astype(np.float64), "tree_nodes": nodes,
+                           "tree_root_N": kids["N"].astype(np.float32), "tree_root_W": kids["W"],
+                           "tree_root_P": kids["P"], "tree_root_mv": kids["mv"].astype(np.float32)})
 
 
 def sim_parts(games, parts=0):
@@ -1038,7 +1141,10 @@ def main():
     eng.set_timing(int(os.environ.get("OAZ_BENCH_TIMING_EVERY", "8")))
     barrier_sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    ready_before_last = 0
+    for k in range(args.steps):
+        if args.dump_outputs and k == args.steps - 1:  # the last step's samples are those buffered after this count
+            ready_before_last = int(eng.selfplay_stats().samples_ready)
         eng.selfplay_step(1)
     barrier_sync()
     elapsed = time.perf_counter() - t0
@@ -1081,7 +1187,7 @@ def main():
     rank_sims = [float(t[0]) for t in gathered]
     rank_s = [float(t[1]) for t in gathered]
 
-    allgather = None
+    allgather = own_recs = None
     if not args.no_allgather:  # C4: RCCL all-gather of (s, pi, z) after the timed region
         from onitama_az.dist import Comm, allgather_sample_bytes, allgather_samples_device
         comm = None
@@ -1091,7 +1197,7 @@ def main():
             if rehearse:  # gloo over host copies (one-GPU rehearsal of the multi-rank script)
                 t1 = time.perf_counter()
                 mine = eng.samples_fetch(int(eng.selfplay_stats().samples_ready))
-                own = len(mine)
+                own, own_recs = len(mine), mine
                 raw = allgather_sample_bytes(torch.from_numpy(mine.view("uint8").copy()), world)
                 total, counts = raw.numel() // 228, None
                 allgather = {"backend": "gloo (rehearsal, host copies)", "seconds": time.perf_counter() - t1}
@@ -1102,6 +1208,10 @@ def main():
                     torch.cuda.synchronize()
                 cs = comm.stats()
                 own = int(cs.own_records)
+                if args.dump_outputs:  # the exchange dropped the samples from the engine: this rank's block of it
+                    from onitama_az.dist import as_samples
+                    first = sum(counts[:rank]) * 228
+                    own_recs = as_samples(raw[first:first + counts[rank] * 228])
                 recv = (total - own) * 228  # bytes this rank received over the links
                 allgather = {"backend": "oaz_allgather_samples (C ABI: RCCL counts all-gather + grouped broadcasts)",
                              "rccl_ranks": int(cs.ranks), "counts": counts, "collective_ms": cs.allgather_ms,
@@ -1143,6 +1253,8 @@ def main():
         elif "error" not in allgather:
             allgather["error"] = "another rank's exchange failed"
 
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        dump_selfplay(args.dump_outputs, eng, cfg, own_recs, ready_before_last)
     if rank == 0:
         sims_steps = cfg["sims"]  # simulation steps (select -> NN -> expand launches) per bench step
         nn = nn_step_rate(kt, evals, args.steps * sims_steps, cfg["blocks"])
@@ -1233,6 +1345,10 @@ def main():
         out.pop("nn_in_loop", None)
         out.pop("tree_kernels", None)
     if rank == 0:
+        out["full"] = args.full  # false: without the side measurements (roofline, PMC, legs, all-gather, CPU baseline)
+    if rank == 0 and not args.full:
+        print(json.dumps(out), flush=True)
+    if rank == 0 and args.full:
         # the dominant kernel's roofline, on one stream (single_stream_leg): per-launch HIP events
         leg = single_stream_leg(args, cfg, local, cfg["precision"])
         lp = leg["positions"]

@@ -124,3 +124,37 @@ def test_grp_launches_per_ply(bench):
     """k_search_grp launches per ply follow the engine's root-noise chunk (max(16, min(512, sims))): a C2 ply
     (100 simulations) is one launch, the Agent default (5 000) ten."""
     assert [bench.grp_launches_per_ply(s) for s in (8, 16, 100, 512, 1000, 5000)] == [1, 1, 1, 1, 2, 10]
+
+
+def test_plain_run_measures_the_headline_only(bench, monkeypatch):
+    """Without --full every side measurement is off (PMC passes, exact-fp32 / compaction legs, all-gather, CPU
+    baseline); with it they are on and the --no-* options leave single ones out, as before."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (3, 2)
+    assert a.no_pmc and a.no_exact and a.no_allgather and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not (a.no_pmc or a.no_exact or a.no_allgather or a.no_cpu_baseline)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-pmc", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.no_pmc and not a.no_cpu_baseline and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_floats_within_the_limit(bench, tmp_path):
+    """--dump-outputs: float32 / float64 .npy files (integers widened so that they stay exact), a fixed seeded
+    sample of a larger output, never more than 64 MB."""
+    import numpy as np
+    assert bench.DUMP_BYTES == 64 << 20
+    boards = np.array([[(1 << 25) - 1, 3]], dtype=np.uint32)  # a 25-bit board does not fit float32 exactly
+    bench.dump_outputs(tmp_path / "o", {"pi": np.ones((4, 50), np.float32), "boards": boards,
+                                        "cards": np.arange(5, dtype=np.uint8)})
+    got = {p.stem: np.load(p) for p in (tmp_path / "o").glob("*.npy")}
+    assert sorted(got) == ["boards", "cards", "pi"]
+    assert got["pi"].dtype == np.float32 and got["cards"].dtype == np.float32 and got["boards"].dtype == np.float64
+    assert np.array_equal(got["boards"], boards.astype(np.float64))
+    with pytest.raises(AssertionError, match="limit"):
+        bench.dump_outputs(tmp_path / "big", {"x": np.zeros((64 << 20) // 4 + 1, np.float32)})
+    keep = bench.dump_sample(1000, 10)
+    assert len(keep) == 10 and np.all(np.diff(keep) > 0) and np.array_equal(keep, bench.dump_sample(1000, 10))
+    assert np.array_equal(bench.dump_sample(7, 10), np.arange(7))

@@ -8,6 +8,8 @@ if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -3 gpurun_out/smoke.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
+# a --full run: the short bench with its side measurements (CPU baseline included)
+BENCH_ARGS="--full ${BENCH_ARGS:---games 8192 --steps 2 --warmup 1 --cpu-seconds 10}"
 timeout -k 10 600 python bench.py ${BENCH_ARGS:---games 8192 --steps 2 --warmup 1 --cpu-seconds 10} > gpurun_out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -3 gpurun_out/bench.log
 exit $rc

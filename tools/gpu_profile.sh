@@ -3,6 +3,8 @@
 # of the same workload. Each step has its own timeout; stops at the first failure.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
 TAG=${TAG:-prof}
+# both runs are --full ones: the side measurements in the line, the single-stream roofline leg at the end of the trace
+BENCH_ARGS="--full ${BENCH_ARGS:-}"; PROF_ARGS="--full ${PROF_ARGS:-}"
 mkdir -p gpurun_out/prof_$TAG
 PY=$(command -v python3)  # absolute path after `--` (rocprofv3 must not exec a PATH lookup)
 exec 3>&1  # step messages go to the script's stdout, not into a step's redirected output file

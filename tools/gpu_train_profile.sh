@@ -3,6 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
 mkdir -p gpurun_out/prof_train
 PY=$(command -v python3)
+TRAIN_ARGS="--full ${TRAIN_ARGS:-}"  # with the PMC passes and the CPU baseline, as the line documents them
 step() { local name=$1; shift; echo "== $name"; "$@"; local rc=$?; echo "$name rc=$rc"; if [ $rc -ne 0 ]; then exit $rc; fi; }
 step train_bench timeout -k 10 300 python bench.py --mode train ${TRAIN_ARGS:-} --steps 200 --warmup 20 --cpu-seconds 10 > gpurun_out/train_bench.log 2>&1
 tail -1 gpurun_out/train_bench.log | cut -c1-600
