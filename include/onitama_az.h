@@ -20,8 +20,8 @@
  *     independent, also when several threads create and drive engines on one GPU at
  *     once (creation zeroes and uploads on the engine's own stream and waits for it).
  *   - Engine, trainer and communicator calls run on their object's device and restore
- *     the calling thread's current HIP device before returning (so do the pure-MCTS
- *     search on cfg->device); the stateless rules entry points (oaz_movegen, oaz_step,
+ *     the calling thread's current HIP device before returning (so do the pure-MCTS and
+ *     alpha-beta searches on cfg->device); the stateless rules entry points (oaz_movegen, oaz_step,
  *     oaz_current_state, oaz_encode) run on the thread's current device.
  *   - Compute entry points need a gfx950 GPU. Without one oaz_create() returns
  *     NULL and the rules entry points return OAZ_ERR_NO_DEVICE; there is no CPU
@@ -39,6 +39,7 @@
  *   oaz_selfplay_*     <- self_play                           alphazero-training/src/train.rs:35-98
  *   oaz_load_weights   <- AlphaZeroMcts::from_model_file      alphazero-training/src/alphazero_mcts/mod.rs:89-105
  *   oaz_pure_mcts_*    <- Mcts agent (random-rollout UCT)     onitama-game/src/ai/mcts/mcts_arena.rs:56-264, mod.rs:37-52
+ *   oaz_alphabeta_*    <- AlphaBeta agent + Evaluation         onitama-game/src/ai/alpha_beta/mod.rs:35-183, evaluation.rs:24-110
  *   oaz_trainer_*      <- the training loop body               alphazero-training/src/train.rs:264-313
  *                         (ConvResNet::forward(train=true) net.rs:215-232, alphaloss net.rs:234-243,
  *                          nn::Sgd{momentum 0.9} + set_weight_decay train.rs:181-186, opt.backward_step)
@@ -527,6 +528,40 @@ int oaz_pure_mcts_search(const oaz_state* roots, int G, const oaz_pure_mcts_conf
  * last one of each device is kept for the next search (a 1 M-search launch's trees are 64 GB); this frees a
  * device's kept buffer (OAZ_ERR_STATE while a search uses it). */
 int oaz_pure_mcts_release_workspace(int device);
+
+/* ---- alpha-beta agent (the fourth opponent of Evaluator::pit, evaluator.rs:276-312) --------------
+ * The reference's `AlphaBeta` agent (onitama-game/src/ai/alpha_beta/mod.rs:35-183): fail-soft alpha-beta
+ * without move ordering or a table, Red maximising and Blue minimising Evaluation::evaluate
+ * (alpha_beta/evaluation.rs:24-110), moves in card slot / from / to order, a cut-off leaving only the
+ * current card's moves. generate_move (mod.rs:136-170) deepens iteratively, depth = 1 .. max_depth - 1,
+ * and keeps only the last iteration's result, so a run the clock does not cut equals one search to
+ * max_depth - 1 plies: that search runs here, one GPU wave per root with one lane per root move.
+ * search_time is not enforced (as the pure-MCTS agent's). */
+typedef struct oaz_alphabeta_config {
+    int32_t max_depth;   /* 6 (alpha_beta/mod.rs:24); the arena's opponent uses 4 (evaluator.rs:303-306).
+                            Accepted: 2..6 (the reference panics below 2, mod.rs:161) */
+    int32_t device;      /* HIP device the search runs on (its own stream; other work on it is not waited for) */
+    int32_t reserved[2];
+} oaz_alphabeta_config;
+
+typedef struct oaz_alphabeta_stats {
+    uint64_t positions;              /* alpha_beta calls over all roots (mod.rs:46), the last iteration's only */
+    uint64_t max_positions_per_root;
+    uint64_t roots_without_move;     /* roots answered with the pass move (the reference panics, mod.rs:165-167) */
+} oaz_alphabeta_stats;
+
+void oaz_alphabeta_config_default(oaz_alphabeta_config* cfg);   /* AlphaBeta::default, mod.rs:21-28 */
+/* Evaluation::evaluate (evaluation.rs:24-90) on the host (no GPU): colour = s[i].to_move, move_result[i] as
+ * MoveResult, or move_result = NULL for None. The kernel evaluates leaves with the same function body. */
+int oaz_alphabeta_evaluate(const oaz_state* s, const uint8_t* move_result, int n, int32_t* out);
+/* One search per root (colour = root.to_move) to max_depth - 1 plies (AlphaBeta::generate_move, mod.rs:136-170,
+ * over alpha_beta, mod.rs:36-132); out_score = best_score (i32). A root without a legal move returns the pass
+ * move (from = to = 25, piece 0, slot = the mover's first card) and the untouched best_score (INT32_MIN for
+ * Red, INT32_MAX for Blue). Runs on cfg->device on a stream of its own with buffers allocated and freed per
+ * call (36 B per root); the calling thread's current HIP device is restored before the call returns.
+ * max_depth outside 2..6 is OAZ_ERR_ARG, checked before any device is touched. */
+int oaz_alphabeta_search(const oaz_state* roots, int G, const oaz_alphabeta_config* cfg,
+                         oaz_move* out_move, int32_t* out_score, oaz_alphabeta_stats* stats);
 
 #ifdef __cplusplus
 }

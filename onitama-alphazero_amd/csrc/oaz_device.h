@@ -403,6 +403,47 @@ OAZ_HD float hash_value(uint64_t h) {
     return (float)v * (1.0f / 8388608.0f);
 }
 
+// ---- alpha-beta static evaluation: onitama-game/src/ai/alpha_beta/evaluation.rs:24-110 ------------
+// One body for the host entry (oaz_alphabeta_evaluate) and the search kernel (oaz_alphabeta.hip), integer
+// only. The reference's quirks are kept, in closed form:
+//   - king positions are get_msb (common/mod.rs:57-66), 1-based (square n -> n + 1, empty board -> 0), the
+//     temples 0-based squares, and both go through convert_to_2d(v) = (v / 5, v % 5);
+//   - distance() is the f32 Euclidean distance truncated to i32: every squared distance here is an integer
+//     <= 41 (rows 0..5, columns 0..4), where (int)sqrtf is the exact integer floor root, counted below by
+//     the squares 1, 4, 9, 16, 25, 36 it reaches;
+//   - every own pawn adds distance(1, enemy king position) (the pawn's bit value 1, not its square), every
+//     enemy pawn on a square without an own pawn (`else if`) distance(1, my king position); the two
+//     king-to-king terms are equal and cancel;
+//   - PIECE_SQUARE_TABLE[n] = 4 * ((2 - |row - 2|) + (2 - |col - 2|)), summed through row and column masks.
+OAZ_HD int ab_msb_pos(uint32_t v) { return v ? 32 - __builtin_ctz(v) : 0; }
+OAZ_HD int ab_distance(int from, int to) {
+    const int dx = to / 5 - from / 5, dy = to % 5 - from % 5, d2 = dx * dx + dy * dy;
+    return (d2 >= 1) + (d2 >= 4) + (d2 >= 9) + (d2 >= 16) + (d2 >= 25) + (d2 >= 36);
+}
+OAZ_HD int ab_pst_sum(uint32_t p) {
+    constexpr uint32_t kRow = 0xF8000000u, kCol = 0x84210800u;  // row 0, column 0
+    constexpr uint32_t r13 = (kRow >> 5) | (kRow >> 15), r2 = kRow >> 10, c13 = (kCol >> 1) | (kCol >> 3), c2 = kCol >> 2;
+    return 4 * (__builtin_popcount(p & r13) + 2 * __builtin_popcount(p & r2) + __builtin_popcount(p & c13) +
+                2 * __builtin_popcount(p & c2));
+}
+// Evaluation::evaluate(state, color, move_result); won = move_result is Some(RedWin | BlueWin)
+OAZ_HD int32_t alphabeta_evaluate(const oaz_state& s, int color, bool won) {
+    const bool blue = color != OAZ_RED;
+    const int32_t sign = blue ? -1 : 1;
+    if (won) return -sign * 10000;
+    const uint32_t mk = blue ? s.kings[1] : s.kings[0], ek = blue ? s.kings[0] : s.kings[1];
+    const uint32_t mp = blue ? s.pawns[1] : s.pawns[0], ep = blue ? s.pawns[0] : s.pawns[1];
+    const int my_temple = blue ? kBlueTemple : kRedTemple, enemy_temple = blue ? kRedTemple : kBlueTemple;
+    const int mkp = ab_msb_pos(mk), ekp = ab_msb_pos(ek);
+    const int n_mp = __builtin_popcount(mp), n_ep = __builtin_popcount(ep);
+    const uint32_t ep_seen = ep & ~mp;  // the 25-square loop looks at an enemy pawn only where no own pawn is
+    const int32_t pieces = (n_mp - n_ep) * 10 + (__builtin_popcount(mk) - __builtin_popcount(ek)) * 10000;
+    const int32_t temple = ab_distance(mkp, enemy_temple) - ab_distance(ekp, my_temple);
+    const int32_t close = n_mp * ab_distance(1, ekp) - __builtin_popcount(ep_seen) * ab_distance(1, mkp);
+    const int32_t squares = ab_pst_sum(mp) - ab_pst_sum(ep_seen);
+    return sign * (pieces + temple + close + squares);
+}
+
 // f64::total_cmp key (argmax ties and signed zeros as Rust orders them)
 OAZ_HD int64_t total_key(double x) {
     int64_t i = (int64_t)__builtin_bit_cast(uint64_t, x);

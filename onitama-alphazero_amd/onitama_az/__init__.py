@@ -15,6 +15,7 @@ from .selfplay import SelfPlayData, TrainConfig, self_play
 from .evaluator import (AlphaZeroAgent, EloRating, Evaluator, EvaluatorConfig, FightStatistics, PitStatistics,
                         RandomAgent, fight)
 from .pure_mcts import Mcts, pure_mcts_search
+from .alpha_beta import AlphaBeta, alpha_beta_search
 from .trainer import Trainer, train_epochs
 from .train_loop import LoopConfig, Stats, train
 
@@ -24,5 +25,5 @@ __all__ = [
     "AlphaZeroMctsConfig", "ConvResNet", "ConvResNetConfig", "Options", "TrainingAlphaZeroMcts", "reward",
     "SelfPlayData", "TrainConfig", "self_play", "AlphaZeroAgent", "EloRating", "Evaluator", "EvaluatorConfig",
     "FightStatistics", "PitStatistics", "RandomAgent", "fight", "Mcts", "pure_mcts_search", "Trainer", "train_epochs",
-    "LoopConfig", "Stats", "train",
+    "LoopConfig", "Stats", "train", "AlphaBeta", "alpha_beta_search",
 ]

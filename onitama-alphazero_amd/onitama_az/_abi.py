@@ -19,6 +19,7 @@ PAWN, KING = 0, 1
 CAPTURE, RED_WIN, BLUE_WIN, IN_PROGRESS = 0, 1, 2, 3
 EVAL_NN, EVAL_HASH = 0, 1
 FP32, BF16, FP32_SPLIT, FP32_SPLIT16 = 0, 1, 2, 3  # OAZ_FP32 / OAZ_BF16 / OAZ_FP32_SPLIT / OAZ_FP32_SPLIT16
+ERR_ARG = -1
 ERR_RANGE = -7  # OAZ_ERR_RANGE (ABI 1 only; ABI 2 recomputes fp16-range tiles, oaz_nn_fallbacks)
 ERR_CAPACITY = -4
 ERR_COMM = -8
@@ -173,6 +174,14 @@ class oaz_pure_mcts_stats(C.Structure):
                                           "rollouts_capped", "max_nodes", "tree_full")]
 
 
+class oaz_alphabeta_config(C.Structure):
+    _fields_ = [("max_depth", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class oaz_alphabeta_stats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("positions", "max_positions_per_root", "roots_without_move")]
+
+
 class oaz_comm_id(C.Structure):
     _fields_ = [("internal", C.c_char * 128)]
 
@@ -274,6 +283,10 @@ _PROTOS = {
     "oaz_pure_mcts_search": (C.c_int, [_VOIDP, C.c_int, _P(oaz_pure_mcts_config), _VOIDP, _VOIDP,
                                        _P(oaz_pure_mcts_stats), _VOIDP, C.c_size_t]),
     "oaz_pure_mcts_release_workspace": (C.c_int, [C.c_int]),
+    "oaz_alphabeta_config_default": (None, [_P(oaz_alphabeta_config)]),
+    "oaz_alphabeta_evaluate": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _VOIDP]),
+    "oaz_alphabeta_search": (C.c_int, [_VOIDP, C.c_int, _P(oaz_alphabeta_config), _VOIDP, _VOIDP,
+                                       _P(oaz_alphabeta_stats)]),
     "oaz_train_config_default": (None, [_P(oaz_train_config)]),
     "oaz_trainer_create": (_VOIDP, [_P(oaz_train_config), C.c_int]),
     "oaz_trainer_destroy": (None, [_VOIDP]),

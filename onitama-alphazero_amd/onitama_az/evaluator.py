@@ -91,10 +91,11 @@ class FightStatistics:  # evaluator.rs:37-110
 
 
 @dataclass
-class PitStatistics:  # evaluator.rs:112-118 (the alpha-beta opponent is out of scope)
+class PitStatistics:  # evaluator.rs:112-118
     self_fight: FightStatistics
     random_fight: Optional[FightStatistics] = None
     mcts_fight: Optional[FightStatistics] = None
+    alphabeta_fight: Optional[FightStatistics] = None  # only from pit(alphabeta=True)
 
 
 @dataclass
@@ -244,7 +245,8 @@ class Evaluator:  # evaluator.rs:139-193
                  ratings: Sequence[Tuple[float, float]] = ((800.0, 800.0), (800.0, 800.0), (800.0, 800.0))):
         self.config, self.best, self.new, self.ratings = config, best, new, ratings
 
-    def pit(self, sims: int = 400, concurrent: bool = True) -> Tuple[PitStatistics, bool]:
+    def pit(self, sims: int = 400, concurrent: bool = True, alphabeta: bool = False,
+            enforce_search_time: bool = True) -> Tuple[PitStatistics, bool]:
         """evaluator.rs:169-193. The reference starts the fights on threads of their own, each with
         its own copy of the networks (`VarStore::copy`, evaluator.rs:206-231); here each fight gets
         weight copies too, so every fight searches on engines of its own and the fights run at the
@@ -252,8 +254,15 @@ class Evaluator:  # evaluator.rs:139-193
         so three tails overlap on one GPU). The fights share nothing, so their statistics equal the
         one-after-the-other run (concurrent=False). Device memory: four search engines of game_amnt
         trees each (1 + 40 sims nodes of 32 B per tree: 134 GB at 65 536 games x 400 sims), all
-        released when pit returns."""
-        cfg = AlphaZeroMctsConfig(search_time=0.4, max_playouts=sims, train=False)  # evaluator.rs:198-204
+        released when pit returns.
+
+        alphabeta=True adds the reference's fourth fight (fight_against_alphabeta, evaluator.rs:276-312): a
+        fifth network copy against AlphaBeta{max_depth 4, 400 ms}, rated by ratings[3] when given (else
+        800 / 800), run and released like the other three. Off by default: the three fights above are then
+        exactly what they were. enforce_search_time=False runs every network search to exactly `sims`
+        playouts whatever the clock says (AlphaZeroMctsConfig.enforce_search_time), for runs that are compared."""
+        cfg = AlphaZeroMctsConfig(search_time=0.4, max_playouts=sims, train=False,  # evaluator.rs:198-204
+                                  enforce_search_time=enforce_search_time)
         from .pure_mcts import Mcts  # evaluator.rs:314-353: Mcts{400 ms, min visits 5, c 1.41, 400 playouts}
 
         def copy(m: ConvResNet) -> ConvResNet:  # train_vs.copy(self.new_nn_vs)
@@ -270,6 +279,14 @@ class Evaluator:  # evaluator.rs:139-193
                                seed=self.config.seed, device=self.new.options.device), *self.ratings[2]),
         ]
         owned = [[models[0], models[1]], [models[2]], [models[3]]]  # each fight's network copies
+        if alphabeta:
+            from .alpha_beta import AlphaBeta  # evaluator.rs:303-306: AlphaBeta{max_depth 4, 400 ms}
+            models.append(copy(self.new))
+            ab_ratings = self.ratings[3] if len(self.ratings) > 3 else (800.0, 800.0)
+            fights.append(lambda: fight(self.config, AlphaZeroAgent(cfg, models[4]),
+                                        AlphaBeta(max_depth=4, search_time=0.4, device=self.new.options.device),
+                                        *ab_ratings))
+            owned.append([models[4]])
 
         def release(ms):  # a fight's engines (the reference drops each fight's VarStores)
             for m in ms:
@@ -280,15 +297,13 @@ class Evaluator:  # evaluator.rs:139-193
         try:
             if concurrent:
                 with ThreadPoolExecutor(max_workers=len(fights)) as pool:  # handles joined in order
-                    self_fight, random_fight, mcts_fight = [f.result() for f in [pool.submit(f) for f in fights]]
+                    out = [f.result() for f in [pool.submit(f) for f in fights]]
             else:  # one fight after the other, each fight's engines released when it ends
                 out = []
                 for f, ms in zip(fights, owned):
                     out.append(f())
                     release(ms)
-                self_fight, random_fight, mcts_fight = out
         finally:
             for ms in owned:
                 release(ms)
-        return (PitStatistics(self_fight, random_fight, mcts_fight),
-                self_fight.winrate > self.config.winrate_percent)
+        return PitStatistics(*out), out[0].winrate > self.config.winrate_percent
