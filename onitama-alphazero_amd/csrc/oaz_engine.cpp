@@ -3,7 +3,7 @@
 // Owns the device buffers of one engine (one GPU), orchestrates the per-simulation kernel
 // sequence  select -> evaluate -> expand/backup  for all G games in lock step, and the
 // per-move finalisation (search result or self-play ply). No compute happens on the host
-// except weight folding/packing, deck dealing for host helpers and sqrt tables.
+// except weight folding/packing (oaz_pack.cpp), deck dealing for host helpers and sqrt tables.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -23,6 +23,7 @@
 #include "oaz_device.h"
 #include "oaz_host.h"
 #include "oaz_kernels.h"
+#include "oaz_pack.h"
 
 using namespace oaz;
 
@@ -165,359 +166,6 @@ extern "C" void oaz_hash_eval(const oaz_state* s, float policy[50], float* value
     const uint64_t h = hash_state(*s);
     for (int i = 0; i < 50; ++i) policy[i] = hash_policy(h, i);
     *value = hash_value(h);
-}
-
-// ---- weights: canonical (tch VarStore order) -> BN-folded -> MFMA-packed ----------------------
-// Canonical order (DESIGN.md "Weights"): conv_init_1.{weight,bias}, bn1.{weight,bias,
-// running_mean,running_var}, for each block i, j in {1,2}: resnet_i.resnet_small_block{j}.
-// {small_block_conv.{weight,bias}, small_block_bn.{4}}, vh_conv.{w,b}, vh_bn.{4},
-// vh_linear1.{w,b}, vh_linear2.{w,b}, policy_conv.{w,b}, policy_bn.{4}, ph_linear2.{w,b}.
-struct FoldedConv {
-    std::vector<float> w;  // [cout][cin][taps]
-    std::vector<float> b;  // [cout]
-};
-
-static FoldedConv fold(const float*& p, int cout, int cin, int taps) {
-    FoldedConv f;
-    const float* w = p;
-    p += (size_t)cout * cin * taps;
-    const float* b = p;
-    p += cout;
-    const float *g = p, *beta = p + cout, *mean = p + 2 * cout, *var = p + 3 * cout;
-    p += 4 * cout;
-    f.w.resize((size_t)cout * cin * taps);
-    f.b.resize(cout);
-    for (int o = 0; o < cout; ++o) {
-        const double s = (double)g[o] / sqrt((double)var[o] + 1e-5);  // BN eval, eps 1e-5
-        for (size_t k = 0; k < (size_t)cin * taps; ++k)
-            f.w[(size_t)o * cin * taps + k] = (float)((double)w[(size_t)o * cin * taps + k] * s);
-        f.b[o] = (float)(((double)b[o] - (double)mean[o]) * s + (double)beta[o]);
-    }
-    return f;
-}
-
-// B fragments of v_mfma_f32_16x16x4f32 for a 64->64 conv: lane l supplies B[k=l>>4][col=l&15];
-// k-group g of tap t covers channels ci = 16g + 4(l>>4) + q, q = 0..3; N-tile nt = 16 columns.
-static void pack_conv64(const FoldedConv& f, std::vector<float>& out) {
-    for (int t = 0; t < 9; ++t)
-        for (int g = 0; g < 4; ++g)
-            for (int nt = 0; nt < 4; ++nt)
-                for (int l = 0; l < 64; ++l)
-                    for (int q = 0; q < 4; ++q) {
-                        const int co = nt * 16 + (l & 15);
-                        const int ci = 16 * g + 4 * (l >> 4) + q;
-                        out.push_back(f.w[((size_t)co * 64 + ci) * 9 + t]);
-                    }
-    for (int o = 0; o < 64; ++o) out.push_back(f.b[o]);
-}
-
-// bf16 B fragments of v_mfma_f32_16x16x32_bf16: for K-half m, lane l supplies
-// B[k = 8(l>>4) + e][col l&15] = W[co = 16nt + (l&15)][ci = 32m + 8(l>>4) + e][tap t].
-static uint16_t f32_to_bf16(float f) {  // round to nearest even
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-static void pack_conv64_bf16(const FoldedConv& f, std::vector<float>& out) {
-    std::vector<uint16_t> h;
-    h.reserve(9 * 2 * 4 * 64 * 8);
-    for (int t = 0; t < 9; ++t)
-        for (int m = 0; m < 2; ++m)
-            for (int nt = 0; nt < 4; ++nt)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 8; ++e) {
-                        const int co = nt * 16 + (l & 15);
-                        const int ci = 32 * m + 8 * (l >> 4) + e;
-                        h.push_back(f32_to_bf16(f.w[((size_t)co * 64 + ci) * 9 + t]));
-                    }
-    const size_t base = out.size();
-    out.resize(base + h.size() / 2);
-    memcpy(out.data() + base, h.data(), h.size() * sizeof(uint16_t));
-    for (int o = 0; o < 64; ++o) out.push_back(f.b[o]);
-}
-
-// fp32 split (OAZ_FP32_SPLIT): w = hi + mid + lo exactly, each term the top 16 bits of an fp32
-// (8 significant bits: bf16). hi = trunc(w), mid = trunc(w - hi), lo = w - hi - mid (both
-// subtractions exact, lo has <= 8 significant bits). Same split as split3() in oaz_nn.hip.
-static void split3_host(float w, uint16_t out[3]) {
-    auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
-    auto from = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
-    const uint32_t h = bits(w) & 0xffff0000u;
-    const float r = w - from(h);
-    const uint32_t m = bits(r) & 0xffff0000u;
-    const float l = r - from(m);
-    out[0] = (uint16_t)(h >> 16);
-    out[1] = (uint16_t)(m >> 16);
-    out[2] = (uint16_t)(bits(l) >> 16);
-}
-
-// Split B fragments: [tap][K-half m][piece p][N-tile][lane] bf16x8, lane l supplying
-// B[k = 8(l>>4) + e][col l&15] = piece p of W[co = 16nt + (l&15)][ci = 32m + 8(l>>4) + e][tap].
-static void pack_conv64_split(const FoldedConv& f, std::vector<float>& out) {
-    std::vector<uint16_t> h;
-    h.reserve(9 * 2 * 3 * 4 * 64 * 8);
-    for (int t = 0; t < 9; ++t)
-        for (int m = 0; m < 2; ++m)
-            for (int pc = 0; pc < 3; ++pc)
-                for (int nt = 0; nt < 4; ++nt)
-                    for (int l = 0; l < 64; ++l)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = nt * 16 + (l & 15);
-                            const int ci = 32 * m + 8 * (l >> 4) + e;
-                            uint16_t s[3];
-                            split3_host(f.w[((size_t)co * 64 + ci) * 9 + t], s);
-                            h.push_back(s[pc]);
-                        }
-    const size_t base = out.size();
-    out.resize(base + h.size() / 2);
-    memcpy(out.data() + base, h.data(), h.size() * sizeof(uint16_t));
-    for (int o = 0; o < 64; ++o) out.push_back(f.b[o]);
-}
-
-// fp16 split (OAZ_FP32_SPLIT16): hi = fp16(x) (round to nearest even), lo = fp16(x - hi); the same
-// split as epilogue_h3_pack in oaz_nn.hip. Weights are first scaled by s = 2^k per output channel so
-// that max |w s| lies in [2^14, 2^15): the top of fp16's range (products with activations < 65504
-// stay far inside fp32), which keeps hi normal for weights down to 2^-28 of the channel's largest and
-// bounds each weight's representation error by 2^-25 / s = 2^-39 max|w| (a channel with one huge
-// weight no longer pushes its ordinary weights into fp16 subnormals). 1/s is stored for the epilogue.
-static void split16_host(float x, uint16_t out[2]) {
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)(x - (float)h);
-    memcpy(&out[0], &h, 2);
-    memcpy(&out[1], &l, 2);
-}
-static float pow2_scale(const float* w, size_t n, size_t stride, float* inv) {
-    float mx = 0.0f;
-    for (size_t k = 0; k < n; ++k) mx = fmaxf(mx, fabsf(w[k * stride]));
-    if (!(mx > 0.0f) || !std::isfinite(mx)) {
-        *inv = 1.0f;
-        return 1.0f;
-    }
-    int e = 0;
-    (void)frexpf(mx, &e);  // mx = f 2^e, f in [0.5, 1)
-    if (e < -100) e = -100;  // keep s and 1/s normal floats
-    *inv = ldexpf(1.0f, e - 15);
-    return ldexpf(1.0f, 15 - e);
-}
-
-// Split16 B fragments: [tap][K-half m][piece p][N-tile][lane] f16x8, lane l supplying
-// B[k = 8(l>>4) + e][col l&15] = piece p of s_co W[co = 16nt + (l&15)][ci = 32m + 8(l>>4) + e][tap];
-// then bias[64], 1/s[64].
-static void pack_conv64_split16(const FoldedConv& f, std::vector<float>& out) {
-    float sc[64], inv[64];
-    for (int co = 0; co < 64; ++co) sc[co] = pow2_scale(&f.w[(size_t)co * 64 * 9], 64 * 9, 1, &inv[co]);
-    std::vector<uint16_t> h;
-    h.reserve(9 * 2 * 2 * 4 * 64 * 8);
-    for (int t = 0; t < 9; ++t)
-        for (int m = 0; m < 2; ++m)
-            for (int pc = 0; pc < 2; ++pc)
-                for (int nt = 0; nt < 4; ++nt)
-                    for (int l = 0; l < 64; ++l)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = nt * 16 + (l & 15);
-                            const int ci = 32 * m + 8 * (l >> 4) + e;
-                            uint16_t s2[2];
-                            split16_host(f.w[((size_t)co * 64 + ci) * 9 + t] * sc[co], s2);  // exact scaling
-                            h.push_back(s2[pc]);
-                        }
-    const size_t base = out.size();
-    out.resize(base + h.size() / 2);
-    memcpy(out.data() + base, h.data(), h.size() * sizeof(uint16_t));
-    for (int o = 0; o < 64; ++o) out.push_back(f.b[o]);
-    for (int o = 0; o < 64; ++o) out.push_back(inv[o]);
-}
-
-// First layer (k_nn_sq16): the 4 bitboard planes go through MFMA (lane l supplies
-// W[co = 16nt + (l&15)][plane l>>4][tap t]); the 16 card planes and the blue-to-move plane
-// (constant over the board, common.rs:68-77,32-37) become T[square][c][co] = sum over the
-// on-board taps of W[co][plane][tap], with c = card index or 16 for the colour plane.
-static void pack_first_layer(const FoldedConv& f, std::vector<float>& out) {
-    for (int t = 0; t < 9; ++t)
-        for (int nt = 0; nt < 4; ++nt)
-            for (int l = 0; l < 64; ++l) out.push_back(f.w[((size_t)(nt * 16 + (l & 15)) * 21 + (l >> 4)) * 9 + t]);
-    for (int o = 0; o < 64; ++o) out.push_back(f.b[o]);
-    for (int sq = 0; sq < 25; ++sq)
-        for (int c = 0; c < 17; ++c) {
-            const int plane = c < 16 ? 4 + c : 20;
-            for (int co = 0; co < 64; ++co) {
-                double acc = 0.0;
-                for (int t = 0; t < 9; ++t) {
-                    const int r = sq / 5 + t / 3 - 1, cc = sq % 5 + t % 3 - 1;
-                    if (r < 0 || r > 4 || cc < 0 || cc > 4) continue;
-                    acc += (double)f.w[((size_t)co * 21 + plane) * 9 + t];
-                }
-                out.push_back((float)acc);
-            }
-        }
-}
-
-static int pack_weights(const float* raw, int blocks, int precision, std::vector<float>& out) {
-    out.clear();
-    out.reserve(nn_packed_floats(blocks, precision));
-    const float* p = raw;
-    pack_first_layer(fold(p, 64, 21, 9), out);
-    for (int b = 0; b < blocks; ++b)
-        for (int j = 0; j < 2; ++j) {
-            if (precision == OAZ_BF16) pack_conv64_bf16(fold(p, 64, 64, 9), out);
-            else if (precision == OAZ_FP32_SPLIT) pack_conv64_split(fold(p, 64, 64, 9), out);
-            else if (precision == OAZ_FP32_SPLIT16) pack_conv64_split16(fold(p, 64, 64, 9), out);
-            else pack_conv64(fold(p, 64, 64, 9), out);
-        }
-    // value head: vh_conv + vh_bn folded, vh_linear1, vh_linear2
-    FoldedConv vc = fold(p, 1, 64, 1);
-    for (int c = 0; c < 64; ++c) out.push_back(vc.w[c]);
-    out.push_back(vc.b[0]);
-    for (int i = 0; i < 3; ++i) out.push_back(0.0f);
-    for (int q = 0; q < 25; ++q)  // vh_linear1.weight [64][25], stored transposed [25][64] (coalesced per lane)
-        for (int o = 0; o < 64; ++o) out.push_back(p[o * 25 + q]);
-    p += 64 * 25;
-    for (int i = 0; i < 64; ++i) out.push_back(*p++);       // vh_linear1.bias
-    for (int i = 0; i < 64; ++i) out.push_back(*p++);       // vh_linear2.weight [1][64]
-    out.push_back(*p++);                                    // vh_linear2.bias
-    for (int i = 0; i < 3; ++i) out.push_back(0.0f);
-    // policy head: policy_conv + policy_bn folded, ph_linear2
-    FoldedConv pc = fold(p, 2, 64, 1);
-    for (int i = 0; i < 128; ++i) out.push_back(pc.w[i]);
-    out.push_back(pc.b[0]);
-    out.push_back(pc.b[1]);
-    out.push_back(0.0f);
-    out.push_back(0.0f);
-    for (int f = 0; f < 50; ++f)  // ph_linear2.weight [50 out][50 in], stored transposed [in][out]
-        for (int o = 0; o < 50; ++o) out.push_back(p[o * 50 + f]);
-    p += 2500;
-    for (int i = 0; i < 50; ++i) out.push_back(*p++);    // ph_linear2.bias
-    out.push_back(0.0f);
-    out.push_back(0.0f);
-    if (precision == OAZ_FP32_SPLIT) {
-        // k_nn_x6 head 1x1 convs on MFMA: split B pieces [K-half m][piece][lane] bf16x8, lane l
-        // supplying B[k = 8(l>>4) + e][col n = l&15] for channel 32m + 8(l>>4) + e, columns
-        // n = 0 value conv, 1 / 2 policy conv planes, 3..15 zero
-        std::vector<uint16_t> h;
-        for (int m = 0; m < 2; ++m)
-            for (int pcs = 0; pcs < 3; ++pcs)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 8; ++e) {
-                        const int c = 32 * m + 8 * (l >> 4) + e, n = l & 15;
-                        const float w = n == 0 ? vc.w[c] : n <= 2 ? pc.w[(n - 1) * 64 + c] : 0.0f;
-                        uint16_t sp[3];
-                        split3_host(w, sp);
-                        h.push_back(sp[pcs]);
-                    }
-        const size_t base = out.size();
-        out.resize(base + h.size() / 2);
-        memcpy(out.data() + base, h.data(), h.size() * sizeof(uint16_t));
-    }
-    if (precision == OAZ_BF16) {
-        // k_nn_h3 in bf16 mode (k_nn_h1): head 1x1 convs as [K-half m][lane] bf16x8, lane l supplying
-        // B[k = 8(l>>4) + e][col n = l&15] for channel 32m + 8(l>>4) + e, columns n = 0 value conv,
-        // 1 / 2 policy conv planes, 3..15 zero
-        std::vector<uint16_t> h;
-        for (int m = 0; m < 2; ++m)
-            for (int l = 0; l < 64; ++l)
-                for (int e = 0; e < 8; ++e) {
-                    const int c = 32 * m + 8 * (l >> 4) + e, n = l & 15;
-                    h.push_back(f32_to_bf16(n == 0 ? vc.w[c] : n <= 2 ? pc.w[(n - 1) * 64 + c] : 0.0f));
-                }
-        const size_t base = out.size();
-        out.resize(base + h.size() / 2);
-        memcpy(out.data() + base, h.data(), h.size() * sizeof(uint16_t));
-    }
-    if (precision == OAZ_FP32_SPLIT16) {
-        // k_nn_h3 head 1x1 convs: [K-half m][piece][lane] f16x8 of the column-scaled weights
-        // (column n = 0 value conv, 1 / 2 policy conv planes, 3..15 zero), then 1/s per column (+pad)
-        float sc[3], inv[4] = {1.0f, 1.0f, 1.0f, 0.0f};
-        sc[0] = pow2_scale(vc.w.data(), 64, 1, &inv[0]);
-        sc[1] = pow2_scale(pc.w.data(), 64, 1, &inv[1]);
-        sc[2] = pow2_scale(pc.w.data() + 64, 64, 1, &inv[2]);
-        std::vector<uint16_t> h;
-        for (int m = 0; m < 2; ++m)
-            for (int pcs = 0; pcs < 2; ++pcs)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 8; ++e) {
-                        const int c = 32 * m + 8 * (l >> 4) + e, n = l & 15;
-                        const float w = n == 0 ? vc.w[c] * sc[0] : n <= 2 ? pc.w[(n - 1) * 64 + c] * sc[n] : 0.0f;
-                        uint16_t sp[2];
-                        split16_host(w, sp);
-                        h.push_back(sp[pcs]);
-                    }
-        const size_t base = out.size();
-        out.resize(base + h.size() / 2);
-        memcpy(out.data() + base, h.data(), h.size() * sizeof(uint16_t));
-        for (int k = 0; k < 4; ++k) out.push_back(inv[k]);
-    }
-    if (precision == OAZ_FP32_SPLIT16 || precision == OAZ_BF16) {
-        // k_nn_h3 first layer on fp16 MFMA (both modes): K block 0 = [piece][N-tile][lane] f16x8, lane
-        // l supplying A[row co = 16nt + (l&15)][k = 8q + e] (q = l>>4) = piece of s_co W[co][plane q][tap e];
-        // K block 1 per square = [square][piece][N-tile][lane] f16x8 with k = 8q + e: e = 0 tap 8 of
-        // plane q, e >= 1 the table T[sq][c = 7q + e - 1][co] (c < 17: the 16 card planes and the
-        // colour plane summed over the square's on-board taps); then 1/s[64]. s = 2^k per output
-        // channel over all of them (max |s w| in [2^14, 2^15)).
-        const float* r1 = raw;  // (fold advances its pointer)
-        FoldedConv f1 = fold(r1, 64, 21, 9);
-        std::vector<float> T((size_t)25 * 17 * 64);
-        for (int sq = 0; sq < 25; ++sq)
-            for (int c = 0; c < 17; ++c) {
-                const int plane = c < 16 ? 4 + c : 20;
-                for (int co = 0; co < 64; ++co) {
-                    double acc = 0.0;
-                    for (int t = 0; t < 9; ++t) {
-                        const int r = sq / 5 + t / 3 - 1, cc = sq % 5 + t % 3 - 1;
-                        if (r < 0 || r > 4 || cc < 0 || cc > 4) continue;
-                        acc += (double)f1.w[((size_t)co * 21 + plane) * 9 + t];
-                    }
-                    T[((size_t)sq * 17 + c) * 64 + co] = (float)acc;
-                }
-            }
-        float s1[64], inv1[64];
-        for (int co = 0; co < 64; ++co) {
-            float mx = 0.0f;
-            for (int pl = 0; pl < 4; ++pl)
-                for (int t = 0; t < 9; ++t) mx = fmaxf(mx, fabsf(f1.w[((size_t)co * 21 + pl) * 9 + t]));
-            for (int sq = 0; sq < 25; ++sq)
-                for (int c = 0; c < 17; ++c) mx = fmaxf(mx, fabsf(T[((size_t)sq * 17 + c) * 64 + co]));
-            s1[co] = pow2_scale(&mx, 1, 1, &inv1[co]);
-        }
-        auto frag = [&](int blk, int sq, std::vector<uint16_t>& h1) {  // blk 0 (sq unused) or 1
-            for (int pcs = 0; pcs < 2; ++pcs)
-                for (int nt = 0; nt < 4; ++nt)
-                    for (int l = 0; l < 64; ++l)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = nt * 16 + (l & 15), q = l >> 4;
-                            float w = 0.0f;
-                            if (blk == 0) w = f1.w[((size_t)co * 21 + q) * 9 + e];
-                            else if (e == 0) w = f1.w[((size_t)co * 21 + q) * 9 + 8];
-                            else if (7 * q + e - 1 < 17) w = T[((size_t)sq * 17 + 7 * q + e - 1) * 64 + co];
-                            uint16_t sp[2];
-                            split16_host(w * s1[co], sp);  // exact scaling
-                            h1.push_back(sp[pcs]);
-                        }
-        };
-        std::vector<uint16_t> h1;
-        frag(0, 0, h1);
-        for (int sq = 0; sq < 25; ++sq) frag(1, sq, h1);
-        const size_t b1 = out.size();
-        out.resize(b1 + h1.size() / 2);
-        memcpy(out.data() + b1, h1.data(), h1.size() * sizeof(uint16_t));
-        for (int co = 0; co < 64; ++co) out.push_back(inv1[co]);
-    }
-    if (out.size() != nn_packed_floats(blocks, precision)) return oaz_set_err(OAZ_ERR_STATE, "pack: size mismatch");
-    if ((size_t)(p - raw) != oaz_weight_count(blocks, 64, 21)) return oaz_set_err(OAZ_ERR_STATE, "pack: raw size mismatch");
-    if (precision == OAZ_FP32_SPLIT16) {
-        // k_nn_h3 recomputes fp16-range tiles with the k_nn_x6 body: the OAZ_FP32_SPLIT blob follows
-        std::vector<float> x6;
-        if (int rc = pack_weights(raw, blocks, OAZ_FP32_SPLIT, x6)) return rc;
-        out.insert(out.end(), x6.begin(), x6.end());
-    }
-    return 0;
-}
-
-// Device floats of an engine's packed weights (SPLIT16 carries the SPLIT blob for its fallback).
-static size_t weights_floats(int blocks, int precision) {
-    return nn_packed_floats(blocks, precision) +
-           (precision == OAZ_FP32_SPLIT16 ? nn_packed_floats(blocks, OAZ_FP32_SPLIT) : 0);
 }
 
 // ---- rules context (no engine needed) ----------------------------------------------------------
@@ -954,7 +602,7 @@ extern "C" oaz_engine* oaz_create(const oaz_config* cfg, int device) {
         dalloc(&e->stats, G * GS_COUNT) || dalloc(&e->stats_sum, (size_t)GS_COUNT) ||
         dalloc(&e->sqrt_tab, (size_t)cfg->sims + 2) || dalloc(&e->policy, G * 50) ||
         dalloc(&e->value, G) || dalloc(&e->need, G) || dalloc(&e->slot, G) || dalloc(&e->cstate, G + 16) ||
-        dalloc(&e->bcnt, (size_t)buckets_of((uint32_t)G) + kMaxParts) || dalloc(&e->weights, weights_floats(cfg->blocks, cfg->precision)) ||
+        dalloc(&e->bcnt, (size_t)buckets_of((uint32_t)G) + kMaxParts) || dalloc(&e->weights, nn_device_floats(cfg->blocks, cfg->precision)) ||
         dalloc(&e->s_roots, G) || dalloc(&e->s_move, G) || dalloc(&e->s_pi, G * 50) ||
         dalloc(&e->s_rootv, G) || dalloc(&e->s_rootp, G * 50) || dalloc(&e->s_ply, G) ||
         dalloc(&e->root, G) || dalloc(&e->ply, G) || dalloc(&e->seq, G) ||
@@ -1092,7 +740,8 @@ extern "C" int oaz_load_weights(oaz_engine* e, const float* blob, size_t n) {
         return oaz_set_err(OAZ_ERR_WEIGHTS, "load_weights: got %zu floats, need %zu for %d blocks", n, need,
                        e->cfg.blocks);
     std::vector<float> packed;
-    if (int rc = pack_weights(blob, e->cfg.blocks, e->cfg.precision, packed)) return rc;
+    if (int rc = oaz_pack_weights(blob, n, e->cfg.blocks, e->cfg.precision, packed))
+        return oaz_set_err(OAZ_ERR_STATE, "load_weights: pack failed (code %d)", rc);
     OAZ_ON_DEVICE(e->device);
     HIP_TRY(hipMemcpyAsync(e->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));

@@ -6,6 +6,7 @@
 
 #include "../../include/onitama_az.h"
 #include "oaz_device.h"  // noise_t
+#include "oaz_nn_layout.h"  // the packed NN weights: nnl::, nn_packed_floats(), nn_device_floats()
 
 namespace oaz {
 
@@ -95,7 +96,7 @@ struct TileMap {
 inline int32_t buckets_of(uint32_t G) { return (int32_t)((G + kBucket - 1) >> kBucketShift); }
 
 struct NNView {
-    const float* blob;  // packed, BN-folded weights (DESIGN.md "NN weights layout")
+    const float* blob;  // packed, BN-folded weights (oaz_nn_layout.h; DESIGN.md "NN weights layout")
     int32_t blocks;
     int32_t precision;  // OAZ_FP32 (exact fp32 MFMA), OAZ_BF16 (bf16 inputs), OAZ_FP32_SPLIT (bf16x6 split),
                         // OAZ_FP32_SPLIT16 (fp16x3 split)
@@ -119,7 +120,6 @@ hipError_t launch_nn_forward(const NNView& w, const oaz_state* s, int B, float* 
 hipError_t launch_hash_eval(const oaz_state* s, int B, float* policy, float* value, hipStream_t st);
 // gather the leaves the playouts use (t.need) into t.cstate / t.slot / t.bcnt, bucket by bucket
 hipError_t launch_eval_compact(const TreeView& t, hipStream_t st);
-size_t nn_packed_floats(int blocks, int precision);
 
 // MCTS
 hipError_t launch_tree_reset(const TreeView& t, hipStream_t st);

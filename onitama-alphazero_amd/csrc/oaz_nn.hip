@@ -47,22 +47,8 @@ constexpr int kTPW = 13;     // squares per wave group (group 1: 12)
 constexpr int kRS = 72;      // LDS row stride (floats)
 constexpr int kScratch = 128;  // per-wave head scratch (floats)
 constexpr int kLdsFloats = kSB * 25 * kRS + kWaves * kScratch;  // 29824 floats = 119,296 B
-// Packed blob (floats), built by pack_weights() in oaz_engine.cpp:
-//   [L1 B: 9 taps x 4 N-tiles x 64 lanes][L1 bias 64][L1 table: 25 squares x 17 x 64]
-//   blocks x 2 x [W: 9 taps x 4 groups x 4 N-tiles x 64 lanes x 4][bias 64]
-//   value head:  wv[64] bv pad[3] l1w[25][64] (transposed) l1b[64] l2w[64] l2b pad[3]
-//   policy head: wp[2*64] bp[2] pad[2] plw[50 in][50 out] (transposed) plb[50] pad[2]
-constexpr size_t kL1B = 9 * 4 * 64;
-constexpr size_t kL1Table = 25 * 17 * kCh;
-constexpr size_t kW64 = 9 * 4 * 4 * 64 * 4;
-constexpr size_t kValueF = 64 + 4 + 64 * 25 + 64 + 64 + 4;
-constexpr size_t kPolicyF = 128 + 4 + 2500 + 52;
-
-// OAZ_BF16 (k_nn_h3 in bf16 mode): 64->64 conv B fragments are bf16 [9 taps][2 K-halves][4 N-tiles]
-// [64 lanes][8], stored in the float blob as 9*2*4*64*4 floats
-constexpr size_t kW64h = 9 * 2 * 4 * 64 * 4;
-
 }  // namespace nn
+// The packed weight blob (built by oaz_pack.cpp) is laid out in oaz_nn_layout.h: every blob offset below is nnl::.
 
 // Rows of this workgroup: [b0, b0 + kSB) below `end`; row loads are clamped to `cap` rows. Plain
 // tiles cover [0, B); over compacted leaves (TileMap, oaz_kernels.h) workgroup i takes tile i / nb of
@@ -82,8 +68,6 @@ namespace x6 {
 constexpr int kRowB = 384;                  // LDS row: 3 pieces x 64 channels x bf16, no padding
 constexpr int kImageB = nn::kSB * 25 * kRowB;  // 153,600 B
 constexpr int kLdsFloats = kImageB / 4 + nn::kWaves * nn::kScratch;  // 39,424 floats = 157,696 B
-constexpr size_t kW = 9 * 2 * 3 * 4 * 64 * 4;
-constexpr size_t kHeadB = 2 * 3 * 64 * 4;  // head 1x1 convs: [K-half][piece][lane] bf16x8 (after the heads)
 }  // namespace x6
 
 // fp16 split variant (OAZ_FP32_SPLIT16): 64->64 conv B fragments are [9 taps][2 K-halves][2 pieces]
@@ -94,26 +78,12 @@ constexpr int kRowB = 128;                     // LDS row of one piece plane: 64
 constexpr int kPlaneB = nn::kSB * 25 * kRowB;  // 51,200 B per piece plane
 constexpr int kImageB = 2 * kPlaneB;           // 102,400 B
 constexpr int kLdsFloats = kImageB / 4 + nn::kWaves * nn::kScratch;  // 26,624 floats = 106,496 B
-constexpr size_t kW = 9 * 2 * 2 * 4 * 64 * 4;
-constexpr size_t kHeadB = 2 * 2 * 64 * 4 + 4;
-// first layer on fp16 MFMA (k_nn_h3, TR): K block 0 [piece][N-tile][lane] f16x8 (bitboard taps 0-7 of
-// plane q = lane >> 4, square-independent), K block 1 [square][piece][N-tile][lane] f16x8 (tap 8 of
-// plane q, then the 17 constant planes' table T[square]), all scaled by s = 2^k per output channel;
-// then 1/s[64]. The 0/1 B operands are built in-kernel (lut: LDS table of the 8-tap bit patterns).
-constexpr size_t kL1Frag = 2 * 4 * 64 * 4;            // one K block: 2 pieces x 4 N-tiles x 64 lanes x f16x8
-constexpr size_t kL1C = 26 * kL1Frag + nn::kCh;
+// first layer on fp16 MFMA (k_nn_h3, TR; weights: nnl::l1c): K block 0 = bitboard taps 0-7 of plane
+// q = lane >> 4 (square-independent), K block 1 per square = tap 8 of plane q, then the 17 constant planes'
+// table T[square]. The 0/1 B operands are built in-kernel (lut: LDS table of the 8-tap bit patterns).
 constexpr int kLutB = 256 * 16;                       // 256 patterns x f16x8
 constexpr int kLutOff = kLdsFloats * 4;               // after the image + scratch (the fallback's LDS)
 }  // namespace h3
-
-size_t nn_packed_floats(int blocks, int precision) {
-    if (precision == OAZ_FP32_SPLIT16)
-        return nn::kL1B + nn::kCh + nn::kL1Table + (size_t)blocks * 2 * (h3::kW + 2 * nn::kCh) + nn::kValueF +
-               nn::kPolicyF + h3::kHeadB + h3::kL1C;
-    const size_t w = precision == OAZ_BF16 ? nn::kW64h : precision == OAZ_FP32_SPLIT ? x6::kW : nn::kW64;
-    return nn::kL1B + nn::kCh + nn::kL1Table + (size_t)blocks * 2 * (w + nn::kCh) + nn::kValueF + nn::kPolicyF +
-           (precision == OAZ_FP32_SPLIT ? x6::kHeadB : 0) + (precision == OAZ_BF16 ? 2 * 64 * 4 + h3::kL1C : 0);
-}
 
 // Square groups: 4 corners + 4 edges + 5 interior (85 on-board taps) | 8 edges + 4 interior (84).
 __constant__ int8_t c_sq_order[25] = {0, 4, 20, 24, 1, 3, 21, 23, 6, 8, 12, 16, 18,
@@ -266,16 +236,16 @@ __device__ __forceinline__ void read_skip(f32x4 (&skip)[nn::kTPW], const float* 
 template <class LD>
 __device__ __forceinline__ void heads_g(const LD& ld, float* scratch, int s, const float* p, int lane, int b, int B,
                                         float* policy, float* value) {
-    const float* vw = p;
-    const float vb = p[64];
-    const float* l1w = p + 68;
-    const float* l1b = l1w + 64 * 25;
-    const float* l2w = l1b + 64;
-    const float l2b = l2w[64];
-    const float* pp = p + nn::kValueF;
-    const float pb0 = pp[128], pb1 = pp[129];
-    const float* plw = pp + 132;
-    const float* plb = plw + 2500;
+    const float* vw = p + nnl::kWv;
+    const float vb = p[nnl::kBv];
+    const float* l1w = p + nnl::kL1w;
+    const float* l1b = p + nnl::kL1b;
+    const float* l2w = p + nnl::kL2w;
+    const float l2b = p[nnl::kL2b];
+    const float* pp = p + nnl::kWp;
+    const float pb0 = p[nnl::kBp], pb1 = p[nnl::kBp + 1];
+    const float* plw = p + nnl::kPlw;
+    const float* plb = p + nnl::kPlb;
     if (lane < 25) {  // 1x1 convs (value 64->1, policy 64->2) with folded BN, ReLU; lane = square
         float sv = vb, s0 = pb0, s1 = pb1;
         const int row = lane * nn::kSB + s;
@@ -318,13 +288,12 @@ __device__ __forceinline__ void heads_g(const LD& ld, float* scratch, int s, con
 template <int NP>
 __device__ __forceinline__ void heads_mlp(const float* const (&feat)[NP], const int (&bs)[NP], const float* p, int lane,
                                           int B, float* policy, float* value) {
-    const float* l1w = p + 68;
-    const float* l1b = l1w + 64 * 25;
-    const float* l2w = l1b + 64;
-    const float l2b = l2w[64];
-    const float* pp = p + nn::kValueF;
-    const float* plw = pp + 132;
-    const float* plb = plw + 2500;
+    const float* l1w = p + nnl::kL1w;
+    const float* l1b = p + nnl::kL1b;
+    const float* l2w = p + nnl::kL2w;
+    const float l2b = p[nnl::kL2b];
+    const float* plw = p + nnl::kPlw;
+    const float* plb = p + nnl::kPlb;
     float hj[NP], lg[NP];
 #pragma unroll
     for (int q = 0; q < NP; ++q) hj[q] = l1b[lane];
@@ -392,11 +361,11 @@ struct HeadMM {
     float b1, w2, bp, b2;
 };
 __device__ __forceinline__ void heads_mm_fetch(HeadMM& R, const float* p, int wave, int lane) {
-    const float* l1w = p + 68;
-    const float* l1b = l1w + 64 * 25;
-    const float* l2w = l1b + 64;
-    const float* plw = p + nn::kValueF + 132;
-    const float* plb = plw + 2500;
+    const float* l1w = p + nnl::kL1w;
+    const float* l1b = p + nnl::kL1b;
+    const float* l2w = p + nnl::kL2w;
+    const float* plw = p + nnl::kPlw;
+    const float* plb = p + nnl::kPlb;
     const int n = (wave & 3) * 16 + (lane & 15), kq = lane >> 4;
 #pragma unroll
     for (int kk = 0; kk < 13; ++kk) {
@@ -409,7 +378,7 @@ __device__ __forceinline__ void heads_mm_fetch(HeadMM& R, const float* p, int wa
     R.b1 = l1b[lane];
     R.w2 = l2w[lane];
     R.bp = plb[lane < 50 ? lane : 0];
-    R.b2 = l2w[64];
+    R.b2 = p[nnl::kL2b];
 }
 __device__ __forceinline__ void heads_mm(const HeadMM& R, const float* feat, float* tab, int wave, int lane, int b0,
                                          int B, float* policy, float* value) {
@@ -493,13 +462,13 @@ __global__ void __launch_bounds__(64 * nn::kWaves) k_nn_sq16(const oaz_state* __
         f32x4 acc[nn::kTPW];
 #pragma unroll
         for (int j = 0; j < nn::kTPW; ++j) acc[j] = f32x4{};
-        conv_l1(acc, bb, blob, sq, lane, nt, ntiles);
-        conv_l1_const(acc, blob + nn::kL1B + nn::kCh, pinfo[lane & 15], sq, lane, nt, ntiles);
-        epilogue(acc, act, blob + nn::kL1B, nullptr, sq, lane, nt, ntiles);
+        conv_l1(acc, bb, blob + nnl::kL1B, sq, lane, nt, ntiles);
+        conv_l1_const(acc, blob + nnl::kL1Table, pinfo[lane & 15], sq, lane, nt, ntiles);
+        epilogue(acc, act, blob + nnl::kL1Bias, nullptr, sq, lane, nt, ntiles);
         __syncthreads();
     }
 
-    const float* p = blob + nn::kL1B + nn::kCh + nn::kL1Table;
+    const float* p = OAZ_NN_CONVS_AT(blob);
     f32x4 acc[nn::kTPW];
     f32x4 skip[nn::kTPW];
     auto conv = [&](const float* w) {
@@ -510,16 +479,16 @@ __global__ void __launch_bounds__(64 * nn::kWaves) k_nn_sq16(const oaz_state* __
     for (int blk = 0; blk < blocks; ++blk) {
         read_skip(skip, act, sq, lane, nt, ntiles);
         conv(p);  // small block 1: conv + BN + ReLU
-        p += nn::kW64;
+        p += nnl::kConvW<OAZ_FP32>;
         __syncthreads();
         epilogue(acc, act, p, nullptr, sq, lane, nt, ntiles);
-        p += nn::kCh;
+        p += nnl::kConvTail<OAZ_FP32>;
         __syncthreads();
         conv(p);  // small block 2: conv + BN, + skip, ReLU
-        p += nn::kW64;
+        p += nnl::kConvW<OAZ_FP32>;
         __syncthreads();
         epilogue(acc, act, p, skip, sq, lane, nt, ntiles);
-        p += nn::kCh;
+        p += nnl::kConvTail<OAZ_FP32>;
         __syncthreads();
     }
     float* scratch = lds + kImageFloats + wave * nn::kScratch;
@@ -761,7 +730,7 @@ struct X6W {
 };
 __device__ __forceinline__ X6W x6_w(const float* p, int lane, int nt) {
     X6W w;
-    w.r = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)(x6::kW * 4), 0x00020000);
+    w.r = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)(nnl::kConvW<OAZ_FP32_SPLIT> * 4), 0x00020000);
     w.voff = (nt * 64 + lane) * 16;
     return w;
 }
@@ -991,7 +960,7 @@ __device__ __forceinline__ void nn_x6_body(const oaz_state* __restrict__ states,
     };
     {  // encoder + first layer
         L1Regs<GRP> l1;
-        first_layer_x6_fetch<GRP>(l1, blob, lane, nt);
+        first_layer_x6_fetch<GRP>(l1, blob + nnl::kL1B, lane, nt);
         const int b = min(b0 + i, sp.cap - 1);  // an empty tile of a bucket starts past cap
         const uint32_t* w = reinterpret_cast<const uint32_t*>(&states[b]);
         const uint32_t bb = kq == 0 ? w[2] : kq == 1 ? w[0] : kq == 2 ? w[3] : w[1];
@@ -1005,21 +974,21 @@ __device__ __forceinline__ void nn_x6_body(const oaz_state* __restrict__ states,
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < NS; ++j) acc[j] = skip[j] = f32x4{};  // skip: finite for the fma in epilogue_x6
-        first_layer_x6<C, GRP>(acc, l1, blob + nn::kL1B + nn::kCh, bb, pinfo[i], lane, nt);
-        epilogue_x6<C, GRP>(acc, img, blob + nn::kL1B, skip, eo, co, false, true);
+        first_layer_x6<C, GRP>(acc, l1, blob + nnl::kL1Table, bb, pinfo[i], lane, nt);
+        epilogue_x6<C, GRP>(acc, img, blob + nnl::kL1Bias, skip, eo, co, false, true);
         __syncthreads();
     }
     // 2 * blocks convs through one call site (small block 1: conv + BN + ReLU; small block 2:
     // conv + BN, + skip, ReLU)
     stamp(0);
-    const float* p = blob + nn::kL1B + nn::kCh + nn::kL1Table;
+    const float* p = OAZ_NN_CONVS_AT(blob);
     for (int c = 0; c < 2 * blocks; ++c) {
 #pragma unroll
         for (int j = 0; j < NS; ++j) acc[j] = f32x4{};
         conv_x6_run<C, GRP>(acc, img, x6_w(p, lane, nt), lo,
                             std::make_integer_sequence<int, X6PlanOf<GRP, C::KH>::P.nbat>{});
         stamp(1);
-        p += x6::kW;
+        p += nnl::kConvW<OAZ_FP32_SPLIT>;
         uint32_t pk[NS][2][3];
         epilogue_x6_pack<C, GRP>(acc, pk, p, skip, co, c & 1, c & 1);
         stamp(3);
@@ -1027,7 +996,7 @@ __device__ __forceinline__ void nn_x6_body(const oaz_state* __restrict__ states,
         stamp(2);
         epilogue_x6_store<C, GRP>(pk, img, eo);
         stamp(3);
-        p += nn::kCh;
+        p += nnl::kConvTail<OAZ_FP32_SPLIT>;
         __syncthreads();
         stamp(4);
     }
@@ -1035,7 +1004,7 @@ __device__ __forceinline__ void nn_x6_body(const oaz_state* __restrict__ states,
     // per square: rows = positions, columns 0 / 1 / 2 = value, policy planes 0 / 1), then the MLPs
     // per position on the VALU from a feature table in LDS
     {
-        const bf16x8* HB = reinterpret_cast<const bf16x8*>(p + nn::kValueF + nn::kPolicyF);
+        const bf16x8* HB = reinterpret_cast<const bf16x8*>(p + nnl::kHeadB);
         bf16x8 hb[2][3];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
@@ -1065,7 +1034,7 @@ __device__ __forceinline__ void nn_x6_body(const oaz_state* __restrict__ states,
         }
         __syncthreads();  // the image is no longer read: its first 4.8 KB become the feature table
         float* feat = reinterpret_cast<float*>(img);  // [16 positions][80]
-        const float hbias = i == 0 ? p[64] : i == 1 ? p[nn::kValueF + 128] : p[nn::kValueF + 129];
+        const float hbias = i == 0 ? p[nnl::kBv] : i == 1 ? p[nnl::kBp] : p[nnl::kBp + 1];
 #pragma unroll
         for (int q = 0; q < kSqPerWave; ++q) {
             const int sq = wave + q * C::WAVES;
@@ -1181,7 +1150,7 @@ __device__ __forceinline__ void h3_mfma(f32x4 (&acc)[C::NS], const f16x8 (&a)[N]
 }
 
 // B pieces of (tap, K-half) step S for N-tile nt: [step][piece][N-tile][lane] f16x8, buffer loads
-__device__ __forceinline__ X6W h3_w(const float* p, int lane, int nt, int bytes = (int)(h3::kW * 4)) {
+__device__ __forceinline__ X6W h3_w(const float* p, int lane, int nt, int bytes = (int)(nnl::kConvW<OAZ_FP32_SPLIT16> * 4)) {
     X6W w;
     w.r = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, bytes, 0x00020000);
     w.voff = (nt * 64 + lane) * 16;
@@ -1429,7 +1398,7 @@ struct L1H {  // the first layer's A operands (K block 0, and K block 1 of each 
 template <int GRP>
 __device__ __forceinline__ void first_layer_h3f_fetch(L1H<GRP>& R, const float* l1c, int lane, int nt) {
     X6W A;
-    A.r = __builtin_amdgcn_make_buffer_rsrc((void*)l1c, (short)0, (int)(26 * h3::kL1Frag * 4), 0x00020000);
+    A.r = __builtin_amdgcn_make_buffer_rsrc((void*)l1c, (short)0, (int)(nnl::kL1cInv * 4), 0x00020000);
     A.voff = (nt * 64 + lane) * 16;
     auto ld = [&](int blk, int pc) {  // [blk][pc][nt][lane]
         return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(A.r, A.voff, (blk * 2 + pc) * 4 * 64 * 16, 0));
@@ -1489,14 +1458,14 @@ __device__ __forceinline__ void h3_heads(const float* p, char* img, const int (&
                                          int B, float* __restrict__ policy, float* __restrict__ value) {
     const int i = lane & 15, kq = lane >> 4;
     {
-        const float* hp = p + nn::kValueF + nn::kPolicyF;
+        const float* hp = p + nnl::kHeadB;
         const f16x8* HB = reinterpret_cast<const f16x8*>(hp);
         f16x8 hb[2][2];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int pc = 0; pc < 2; ++pc) hb[m][pc] = HB[(C::BF ? m : m * 2 + pc) * 64 + lane];  // BF: [m][lane]
-        const float hs = C::BF ? 1.0f : hp[2 * 2 * 64 * 4 + (i < 3 ? i : 0)];
+        const float hs = C::BF ? 1.0f : hp[(int)nnl::kHeadBLen<OAZ_FP32_SPLIT16> + (i < 3 ? i : 0)];
         // MLP weights in flight during the head convs (after hb: vmcnt is in order)
         HeadMM hm;
         heads_mm_fetch(hm, p, wave, lane);
@@ -1525,7 +1494,7 @@ __device__ __forceinline__ void h3_heads(const float* p, char* img, const int (&
         }
         __syncthreads();  // the image is no longer read: its first 4.8 KB become the feature table
         float* feat = reinterpret_cast<float*>(img);  // [16 positions][80]
-        const float hbias = i == 0 ? p[64] : i == 1 ? p[nn::kValueF + 128] : p[nn::kValueF + 129];
+        const float hbias = i == 0 ? p[nnl::kBv] : i == 1 ? p[nnl::kBp] : p[nnl::kBp + 1];
 #pragma unroll
         for (int q = 0; q < kSqPerWave; ++q) {
             const int sq = wave + q * C::WAVES;
@@ -1556,6 +1525,7 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
     const int tid = (int)threadIdx.x + opaque, wave = tid >> 6, lane = tid & 63;
     const int nt = wave & 3;
     const int b0 = sp.b0;
+    constexpr int kPrec = C::BF ? OAZ_BF16 : OAZ_FP32_SPLIT16;  // the blob's layout
     // (bf16 mode with two image buffers: one piece plane each, so the image area is kImageB as well)
     int* pinfo = reinterpret_cast<int*>(lds + (C::BF && !OAZ_H1_PP ? h3::kPlaneB : h3::kImageB) / 4);
     const int i = lane & 15, kq = lane >> 4;
@@ -1583,10 +1553,7 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         L1H<GRP> l1h;
         // the fp16 first layer's fragments and inverse scales (after the heads; bf16 mode: same section)
         constexpr bool kF16 = !C::BF || OAZ_H1_L1F16;
-        const float* l1c = C::BF ? blob + nn::kL1B + nn::kCh + nn::kL1Table + (size_t)blocks * 2 * (nn::kW64h + nn::kCh) +
-                                       nn::kValueF + nn::kPolicyF + 2 * 64 * 4
-                                 : blob + nn::kL1B + nn::kCh + nn::kL1Table + (size_t)blocks * 2 * (h3::kW + 2 * nn::kCh) +
-                                       nn::kValueF + nn::kPolicyF + h3::kHeadB;
+        const float* l1c = OAZ_NN_L1C_AT(blob, kPrec, blocks);
         // the state loads first: vmcnt retires in issue order, so the pinfo / LUT work before the
         // barrier then waits for these and not for the first-layer operands issued after them
         const int b = min(b0 + i, sp.cap - 1);  // an empty tile of a bucket starts past cap
@@ -1597,7 +1564,7 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         if constexpr (kF16)
             first_layer_h3f_fetch<GRP>(l1h, l1c, lane, nt);
         else
-            first_layer_x6_fetch<GRP>(l1, blob, lane, nt);
+            first_layer_x6_fetch<GRP>(l1, blob + nnl::kL1B, lane, nt);
         if (tid < nn::kSB) {
             const int blue = st.to_move & 1;
             const int c0 = (blue ? st.cards[2] : st.cards[0]) & 15, c1 = (blue ? st.cards[3] : st.cards[1]) & 15;
@@ -1605,7 +1572,7 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         }
         if constexpr (kF16)
             for (int t = tid; t < 512; t += 64 * C::WAVES) l1_lut_build(img + h3::kLutOff, t);
-        const f32x4 bias1t = *reinterpret_cast<const f32x4*>(blob + nn::kL1B + cq);
+        const f32x4 bias1t = *reinterpret_cast<const f32x4*>(blob + nnl::kL1Bias + cq);
         if (b0 >= B) return false;  // an empty tile of a compacted bucket (uniform over the workgroup)
         __syncthreads();
         stamp(6);
@@ -1615,7 +1582,7 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
             first_layer_h3f<C, GRP>(acc, l1h, bb, pinfo[i], lane, reinterpret_cast<const char*>(lds),
                                     std::make_integer_sequence<int, grp_n(GRP)>{});
         else  // exact fp32 MFMA on the 0/1 inputs, as k_nn_x6
-            first_layer_x6<C, GRP>(acc, l1, blob + nn::kL1B + nn::kCh, bb, pinfo[i], lane, nt);
+            first_layer_x6<C, GRP>(acc, l1, blob + nnl::kL1Table, bb, pinfo[i], lane, nt);
         if constexpr (C::DBG == 2) {  // the MFMA results, so the stamp follows the MFMAs
             float z = 0.0f;
 #pragma unroll
@@ -1625,11 +1592,11 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         stamp(7);
         uint32_t pk[NS][2][2];
         const f32x4 inv1 = !kF16 ? f32x4{1.0f, 1.0f, 1.0f, 1.0f}
-                                 : *reinterpret_cast<const f32x4*>(l1c + 26 * h3::kL1Frag + cq);
+                                 : *reinterpret_cast<const f32x4*>(l1c + nnl::kL1cInv + cq);
         epilogue_h3t_pack<C, GRP, true, 0>(acc, pk, bias1t, inv1, skip, hmax);
         if constexpr (h3_pf<C>()) {
-            constexpr size_t kWc = C::BF ? nn::kW64h : h3::kW;
-            h3_first_b<C, GRP>(bpre, h3_w(blob + nn::kL1B + nn::kCh + nn::kL1Table, lane, nt, (int)(kWc * 4)));
+            constexpr size_t kWc = nnl::kConvW<kPrec>;
+            h3_first_b<C, GRP>(bpre, h3_w(OAZ_NN_CONVS_AT(blob), lane, nt, (int)(kWc * 4)));
         }
         epilogue_h3t_store<C, GRP>(pk, img, eot);
         __syncthreads();
@@ -1637,12 +1604,12 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
     // the 2 * blocks convs in pairs, so the residual's role is compile-time (small block 1: conv + BN +
     // ReLU; small block 2: conv + BN, + skip, ReLU, the result kept as the next skip)
     stamp(0);
-    const float* p = blob + nn::kL1B + nn::kCh + nn::kL1Table;
+    const float* p = OAZ_NN_CONVS_AT(blob);
     auto conv_one = [&](auto res, bool more) {
         constexpr int RES = decltype(res)::value;
-        constexpr size_t kWc = C::BF ? nn::kW64h : h3::kW;  // B fragments of one conv
-        const f32x4 bbt = *reinterpret_cast<const f32x4*>(p + kWc + cq);  // in flight during the conv
-        const f32x4 sct = C::BF ? f32x4{1.0f, 1.0f, 1.0f, 1.0f} : *reinterpret_cast<const f32x4*>(p + kWc + nn::kCh + cq);
+        constexpr size_t kWc = nnl::kConvW<kPrec>;  // B fragments of one conv
+        const f32x4 bbt = *reinterpret_cast<const f32x4*>(p + kWc + nnl::kConvBias + cq);  // in flight during the conv
+        const f32x4 sct = C::BF ? f32x4{1.0f, 1.0f, 1.0f, 1.0f} : *reinterpret_cast<const f32x4*>(p + kWc + nnl::kConvInv + cq);
 #pragma unroll
         for (int j = 0; j < NS; ++j) acc[j] = f32x4{};
         // bf16 mode, two buffers: the pair's first conv reads buffer 0 and writes buffer 1, the second
@@ -1656,7 +1623,7 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
                             std::make_integer_sequence<int, H3P<C, GRP>::P.nbat>{});
         stamp(1);
         const float* pc = p;
-        p += C::BF ? nn::kW64h + nn::kCh : h3::kW + 2 * nn::kCh;
+        p += nnl::kConvStride<kPrec>;
         uint32_t pk[NS][2][2];
         epilogue_h3t_pack<C, GRP, false, RES>(acc, pk, bbt, sct, skip, hmax);  // before the barrier: a
         // (unconditional, so that the old pieces are dead during the conv; the last conv reloads its own)
@@ -1793,7 +1760,7 @@ constexpr int kImageB = 2 * kPlaneB;        // hi + lo pieces
 constexpr int kSkipOff = 2 * kImageB;       // two image buffers, then the first layer's fp32 results:
                                             // [4 N-tiles][64 lanes][2 tiles] f32x4
 constexpr int kHeadOff = kSkipOff + 4 * 64 * 2 * 16;  // the head parameters (value, policy, head 1x1 B pieces)
-constexpr int kHeadF = (int)(nn::kValueF + nn::kPolicyF + h3::kHeadB);  // 5,512 floats
+constexpr int kHeadF = (int)nnl::kHeadsLen<OAZ_FP32_SPLIT16>;  // 5,512 floats
 constexpr int kFeatOff = kHeadOff + ((kHeadF * 4 + 15) & ~15);  // features [16][80] + heads_mm's table [16][128]
 constexpr int kBytes = kFeatOff + (16 * 80 + 16 * 128) * 4;
 // 16-byte chunk c8 of a row at c8 ^ (row & 7): the 16 rows a 16-lane group reads spread over the banks
@@ -1890,10 +1857,9 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
     const int cq = nt * 16 + 4 * kq;  // this lane's 4 output channels cq .. cq + 3
     const int eo0 = h3s::chunk_off(sq0, cq >> 3) + (cq & 7) * 2;
     const int eo1 = h3s::chunk_off(live1 ? sq1 : h3s::kZero, cq >> 3) + (cq & 7) * 2;
-    const float* l1c = blob + nn::kL1B + nn::kCh + nn::kL1Table + (size_t)blocks * 2 * (h3::kW + 2 * nn::kCh) +
-                       nn::kValueF + nn::kPolicyF + h3::kHeadB;
-    const float* p = blob + nn::kL1B + nn::kCh + nn::kL1Table;  // the first conv's packed weights
-    const float* ph0 = p + (size_t)blocks * 2 * (h3::kW + 2 * nn::kCh);  // the head parameters
+    const float* l1c = OAZ_NN_L1C_AT(blob, OAZ_FP32_SPLIT16, blocks);
+    const float* p = OAZ_NN_CONVS_AT(blob);  // the first conv's packed weights
+    const float* ph0 = OAZ_NN_HEADS_AT(blob, OAZ_FP32_SPLIT16, blocks);  // the head parameters
     uint32_t hmax = 0;
     auto track = [&](const uint32_t (&pk)[2][2]) {  // the fp16 range guard (hi >= +0 after ReLU)
         hmax = __builtin_bit_cast(
@@ -1933,7 +1899,7 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
             inv1 = *reinterpret_cast<const f32x4*>(res.l1 + h3s::kL1Bytes + 256 + cq * 4);
         } else {
             X6W A;
-            A.r = __builtin_amdgcn_make_buffer_rsrc((void*)l1c, (short)0, (int)(26 * h3::kL1Frag * 4), 0x00020000);
+            A.r = __builtin_amdgcn_make_buffer_rsrc((void*)l1c, (short)0, (int)(nnl::kL1cInv * 4), 0x00020000);
             A.voff = (nt * 64 + lane) * 16;
             auto ld = [&](int blk, int pc) {  // [blk][pc][nt][lane]
                 return __builtin_bit_cast(
@@ -1946,8 +1912,8 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
                 a1[k][0] = ld(1 + c_cls_rep[k], 0);
                 a1[k][1] = ld(1 + c_cls_rep[k], 1);
             }
-            bias1t = *reinterpret_cast<const f32x4*>(blob + nn::kL1B + cq);
-            inv1 = *reinterpret_cast<const f32x4*>(l1c + 26 * h3::kL1Frag + cq);
+            bias1t = *reinterpret_cast<const f32x4*>(blob + nnl::kL1Bias + cq);
+            inv1 = *reinterpret_cast<const f32x4*>(l1c + nnl::kL1cInv + cq);
         }
         const uint32_t bb = kq == 0 ? st.pawns[0] : kq == 1 ? st.kings[0] : kq == 2 ? st.pawns[1] : st.kings[1];
         const int blue = st.to_move & 1;
@@ -2015,9 +1981,10 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
     auto conv_one = [&](auto res, bool more, const char* rd, char* wr) {
         constexpr int RES = decltype(res)::value;
         if (compute) {
-            const f32x4 bbt = *reinterpret_cast<const f32x4*>(p + h3::kW + cq);
-            const f32x4 sct = *reinterpret_cast<const f32x4*>(p + h3::kW + nn::kCh + cq);
-            const X6W Wn = h3_w(p + h3::kW + 2 * nn::kCh, lane, nt);
+            constexpr size_t kWc = nnl::kConvW<OAZ_FP32_SPLIT16>;
+            const f32x4 bbt = *reinterpret_cast<const f32x4*>(p + kWc + nnl::kConvBias + cq);
+            const f32x4 sct = *reinterpret_cast<const f32x4*>(p + kWc + nnl::kConvInv + cq);
+            const X6W Wn = h3_w(p + nnl::kConvStride<OAZ_FP32_SPLIT16>, lane, nt);
             f32x4 acc0 = {}, acc1 = {};
             f16x8 xl0[2], xh0[2], xl1[2], xh1[2];
             {
@@ -2061,7 +2028,7 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
                 store2(wr, eo1, pk);
             }
         }
-        p += h3::kW + 2 * nn::kCh;
+        p += nnl::kConvStride<OAZ_FP32_SPLIT16>;
         __syncthreads();
         stamp(3);
     };
@@ -2075,10 +2042,10 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
     {
         HeadMM hm;
         heads_mm_fetch(hm, hl, wave, lane);
-        const float hs = hl[nn::kValueF + nn::kPolicyF + 2 * 2 * 64 * 4 + (i < 3 ? i : 0)];
-        const float hbias = i == 0 ? hl[64] : i == 1 ? hl[nn::kValueF + 128] : hl[nn::kValueF + 129];
+        const float hs = hl[nnl::kHeadInv<OAZ_FP32_SPLIT16> + (i < 3 ? i : 0)];
+        const float hbias = i == 0 ? hl[nnl::kBv] : i == 1 ? hl[nnl::kBp] : hl[nnl::kBp + 1];
         if (wave == 4 || wave == 5) {
-            const f16x8* HB = reinterpret_cast<const f16x8*>(hl + nn::kValueF + nn::kPolicyF);
+            const f16x8* HB = reinterpret_cast<const f16x8*>(hl + nnl::kHeadB);
             f16x8 hb[2][2];
 #pragma unroll
             for (int m = 0; m < 2; ++m)
@@ -2126,9 +2093,8 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
 
 // The one-launch search's resident operands (H3sResident): all threads of the workgroup, then a barrier.
 __device__ __forceinline__ void h3s_load_resident(char* lds, const float* blob, int blocks) {
-    const float* l1c = blob + nn::kL1B + nn::kCh + nn::kL1Table + (size_t)blocks * 2 * (h3::kW + 2 * nn::kCh) +
-                       nn::kValueF + nn::kPolicyF + h3::kHeadB;
-    const float* ph0 = blob + nn::kL1B + nn::kCh + nn::kL1Table + (size_t)blocks * 2 * (h3::kW + 2 * nn::kCh);
+    const float* l1c = OAZ_NN_L1C_AT(blob, OAZ_FP32_SPLIT16, blocks);
+    const float* ph0 = OAZ_NN_HEADS_AT(blob, OAZ_FP32_SPLIT16, blocks);
     const int tid = (int)threadIdx.x;
     uint4* d = reinterpret_cast<uint4*>(lds + h3s::kL1Off);
     for (int k = tid; k < h3s::kL1Bytes / 16; k += (int)blockDim.x) {  // [slot][pc][nt][lane]
@@ -2137,8 +2103,8 @@ __device__ __forceinline__ void h3s_load_resident(char* lds, const float* blob, 
         d[k] = reinterpret_cast<const uint4*>(l1c)[blk * 512 + rest];
     }
     float* bi = reinterpret_cast<float*>(lds + h3s::kL1BiasOff);
-    if (tid < 64) bi[tid] = blob[nn::kL1B + tid];
-    else if (tid < 128) bi[tid] = l1c[26 * h3::kL1Frag + tid - 64];
+    if (tid < 64) bi[tid] = blob[nnl::kL1Bias + tid];
+    else if (tid < 128) bi[tid] = l1c[nnl::kL1cInv + tid - 64];
     float4* hd = reinterpret_cast<float4*>(lds + h3s::kHeadOff);
     for (int k = tid; k < h3s::kHeadF / 4; k += (int)blockDim.x) hd[k] = reinterpret_cast<const float4*>(ph0)[k];
     __syncthreads();

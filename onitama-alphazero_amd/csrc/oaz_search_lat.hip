@@ -304,7 +304,7 @@ __global__ void __launch_bounds__(kLatThreads) k_search_lat(TreeView t, const oa
     int ran = sims;
     for (int s = 0; s < sims; ++s) {
         if (!hash_eval && !resident) {  // at the start, and after an fp16-range recompute used the whole LDS
-            const float* ph0 = blob + nn::kL1B + nn::kCh + nn::kL1Table + (size_t)blocks * 2 * (h3::kW + 2 * nn::kCh);
+            const float* ph0 = OAZ_NN_HEADS_AT(blob, OAZ_FP32_SPLIT16, blocks);
             float4* hd = reinterpret_cast<float4*>(lb + h3s::kHeadOff);
             for (int k = (int)threadIdx.x; k < h3s::kHeadF / 4; k += kLatThreads)
                 hd[k] = reinterpret_cast<const float4*>(ph0)[k];
