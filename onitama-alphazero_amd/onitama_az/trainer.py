@@ -33,12 +33,17 @@ class EpochLoss:  # the per-epoch line of train.rs:316-324
 
 class Trainer:
     def __init__(self, blocks: int, max_batch: int = 512, learning_rate: float = 5e-3, momentum: float = 0.9,
-                 weight_decay: float = 1e-4, value_loss_broadcast: bool = True, device: int = 0):
+                 weight_decay: float = 1e-4, value_loss_broadcast: bool = True, device: int = 0,
+                 bn_momentum: Optional[float] = None, bn_eps: Optional[float] = None):
         lib = _abi.load()
         cfg = _abi.oaz_train_config()
         lib.oaz_train_config_default(C.byref(cfg))
         cfg.blocks, cfg.max_batch = int(blocks), int(max_batch)
         cfg.learning_rate, cfg.momentum, cfg.weight_decay = learning_rate, momentum, weight_decay
+        if bn_momentum is not None:  # None: the config's own default (tch's 0.1 / 1e-5)
+            cfg.bn_momentum = bn_momentum
+        if bn_eps is not None:
+            cfg.bn_eps = bn_eps
         cfg.value_loss_broadcast = int(bool(value_loss_broadcast))
         h = lib.oaz_trainer_create(C.byref(cfg), int(device))
         if not h:

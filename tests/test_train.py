@@ -10,57 +10,11 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from conftest import random_positions
 from onitama_az import _abi
-from onitama_az.weights import canonical_layout, named_from_blob, random_weights
+from onitama_az.weights import named_from_blob
+from train_util import _batch, _close_grads, _close_params, _run_steps, _weights  # noqa: F401
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "oracle"))
-
-
-def _batch(orc, n, seed):
-    rng = np.random.default_rng(seed)
-    states = random_positions(orc, n, seed=seed)
-    samples = np.zeros(n, dtype=_abi.SAMPLE_DTYPE)
-    samples["state"] = states
-    pi = rng.random((n, 50)) * (rng.random((n, 50)) < 0.3)
-    pi[:, 0] += 1e-3  # never an all-zero row
-    samples["pi"] = (pi / pi.sum(1, keepdims=True)).astype(np.float32)
-    samples["z"] = rng.integers(-1, 2, n).astype(np.float32)
-    planes = np.stack([orc.encode(states[i]) for i in range(n)])
-    return samples, planes
-
-
-def _weights(seed, blocks):
-    """Random init with non-trivial BN affine/running statistics."""
-    rng = np.random.default_rng(seed)
-    w = random_weights(seed, blocks).copy()
-    off = 0
-    for name, shape in canonical_layout(blocks):
-        n = int(np.prod(shape))
-        if name.endswith("running_var"):
-            w[off:off + n] = rng.uniform(0.5, 2.0, n)
-        elif name.endswith("running_mean") or (("bn" in name) and name.endswith("bias")):
-            w[off:off + n] = rng.normal(0, 0.1, n)
-        elif ("bn" in name) and name.endswith("weight"):
-            w[off:off + n] = rng.uniform(0.7, 1.3, n)
-        off += n
-    return w.astype(np.float32)
-
-
-def _close_grads(got, ref):
-    errs = {}
-    for k, g in ref.items():
-        scale = float(np.abs(g).max())
-        errs[k] = (float(np.abs(got[k].reshape(g.shape) - g).max()), scale)
-    worst = sorted(errs.items(), key=lambda kv: -kv[1][0] / (2e-4 * kv[1][1] + 1e-7))[:4]  # closest to the bar
-    print("gradient errors closest to the bar (err, max|g|):", [(k, f"{e:.2e}", f"{sc:.2e}") for k, (e, sc) in worst])
-    for k, (err, scale) in errs.items():
-        assert err <= 2e-4 * scale + 1e-7, (k, err, scale)
-
-
-def _close_params(got, ref):
-    for k, p in ref.items():
-        np.testing.assert_allclose(got[k].reshape(p.shape), p, rtol=1e-5, atol=1e-6, err_msg=k)
 
 
 # ---- CPU: the restatement itself ------------------------------------------------------------------
@@ -99,33 +53,45 @@ def test_trainer_without_device_is_a_loud_error(lib):
         Trainer(blocks=3)
 
 
-# ---- GPU parity ---------------------------------------------------------------------------------
-def _run_steps(orc, blocks, B, steps, broadcast=True, seed=1):
-    from onitama_az.trainer import Trainer
+def test_reference_optimiser_equals_torch_sgd(orc):
+    """train_step's optimiser against torch.optim.SGD(momentum=, weight_decay=) stepping the same float64
+    parameters from the same gradients, at non-default lr / momentum / weight decay: three steps, 1e-12.
+    The hyperparameter cases of tests/test_gpu_train.py lean on this half of the restatement."""
+    import torch
+    from train_ref import RUNNING, train_step
+    blocks, B, steps, lr, mom, wd = 1, 16, 3, 0.03, 0.7, 2e-3
+    samples, planes = _batch(orc, B * steps, 21)
+    named = {k: np.asarray(v, dtype=np.float64) for k, v in named_from_blob(_weights(21, blocks), blocks).items()}
+    params = {k: torch.tensor(v, requires_grad=True) for k, v in named.items() if not k.endswith(RUNNING)}
+    opt = torch.optim.SGD(list(params.values()), lr=lr, momentum=mom, weight_decay=wd)
+    bufs = None
+    for s in range(steps):
+        rows = slice(s * B, (s + 1) * B)
+        named, grads, _, _, bufs = train_step(named, planes[rows], samples["pi"][rows], samples["z"][rows], blocks,
+                                              lr=lr, momentum=mom, wd=wd, bufs=bufs)
+        for k, t in params.items():
+            t.grad = torch.tensor(grads[k])
+        opt.step()
+        for k, t in params.items():
+            assert np.abs(t.detach().numpy() - named[k]).max() <= 1e-12, (s, k)
+
+
+def test_reference_float32_mode_inside_project_bars(orc):
+    """The restatement in float32 against itself in float64 on the _batch / _weights inputs (blocks 2,
+    B 32) stays inside the project's bars: the bars are reachable by a correct fp32 implementation."""
     from train_ref import train_step
-    samples, planes = _batch(orc, B * steps, seed)
-    w = _weights(seed, blocks)
-    named = named_from_blob(w, blocks)
-    with Trainer(blocks=blocks, max_batch=B, value_loss_broadcast=broadcast) as tr:
-        tr.set_weights(w)
-        tr.load_samples(samples)
-        idx = np.arange(B * steps, dtype=np.int32).reshape(steps, B)[:, ::-1].copy()  # non-trivial gather
-        tr.set_batches(idx)
-        bufs = None
-        for s in range(steps):
-            rows = idx[s]
-            named, grads, lv, lp, bufs = train_step(named, planes[rows], samples["pi"][rows], samples["z"][rows],
-                                                    blocks, bufs=bufs, broadcast=broadcast)
-            tr.backward(s)
-            g = named_from_blob(tr.grads(), blocks)
-            _close_grads(g, grads)
-            tr.apply(1.0)
-            v, p, k = tr.losses()
-            assert k == 1
-            assert abs(v - lv) <= 1e-5 * abs(lv) + 1e-7 and abs(p - lp) <= 1e-5 * abs(lp) + 1e-7, (v, lv, p, lp)
-            _close_params(named_from_blob(tr.get_weights(), blocks), named)
+    blocks, B = 2, 32
+    samples, planes = _batch(orc, B, 5)
+    named = named_from_blob(_weights(5, blocks), blocks)
+    p64, g64, lv64, lp64, _ = train_step(named, planes, samples["pi"], samples["z"], blocks)
+    p32, g32, lv32, lp32, _ = train_step(named, planes, samples["pi"], samples["z"], blocks, dtype=np.float32)
+    assert all(g.dtype == np.float32 for g in g32.values()) and all(g.dtype == np.float64 for g in g64.values())
+    _close_grads(g32, g64)
+    assert abs(lv32 - lv64) <= 1e-5 * abs(lv64) and abs(lp32 - lp64) <= 1e-5 * abs(lp64), (lv32, lv64, lp32, lp64)
+    _close_params(p32, p64)
 
 
+# ---- GPU parity ---------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_train_step_matches_reference_restatement(orc):
     _run_steps(orc, blocks=3, B=64, steps=1)
