@@ -242,8 +242,6 @@ __global__ __launch_bounds__(kThreads) void k_alphabeta(const oaz_state* roots, 
     }
 }
 
-static inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace ab
 
 extern "C" void oaz_alphabeta_config_default(oaz_alphabeta_config* c) {  // ai/alpha_beta/mod.rs:21-28
@@ -276,61 +274,47 @@ extern "C" int oaz_alphabeta_search(const oaz_state* roots, int G, const oaz_alp
                                         roots[g].cards[4]) > 15 ||
             ((roots[g].kings[0] | roots[g].kings[1] | roots[g].pawns[0] | roots[g].pawns[1]) & 0x7Fu))
             return oaz_set_err(OAZ_ERR_ARG, "alphabeta: root %d is not a valid state", g);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return oaz_set_err(OAZ_ERR_NO_DEVICE, "alphabeta: no HIP device");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return oaz_set_err(OAZ_ERR_ARG, "alphabeta: device %d of %d", cfg->device, ndev);
+    if (int rc = oaz_check_device("alphabeta", cfg->device)) return rc;
     if (stats) memset(stats, 0, sizeof(*stats));
     if (G == 0) return 0;
     const int plies = cfg->max_depth - 1;
-    // per call: roots, moves, scores, position counts (36 B per root, 256-byte aligned sections); no kept workspace
-    const size_t o_mv = ab::align256(sizeof(oaz_state) * G), o_sc = o_mv + ab::align256(sizeof(oaz_move) * G);
-    const size_t o_pos = o_sc + ab::align256(sizeof(int32_t) * G), bytes = o_pos + sizeof(uint32_t) * G;
     const size_t lds_bytes = sizeof(uint32_t) * (ab::kAttWords + (size_t)(plies > 2 ? plies - 2 : 0) * ab::kFrameWords * ab::kThreads);
-    int rc = 0;
-    auto fail = [&](hipError_t e, const char* what) {
-        rc = oaz_set_err(OAZ_ERR_HIP, "alphabeta: %s: %s", what, hipGetErrorString(e));
+    // per call: roots, moves, scores, position counts (36 B per root); no kept workspace
+    oaz_state* d_roots = nullptr;
+    oaz_move* d_mv = nullptr;
+    int32_t* d_sc = nullptr;
+    uint32_t* d_pos = nullptr;
+    auto carve = [&](Carver c) {
+        d_roots = c.take<oaz_state>(G);
+        d_mv = c.take<oaz_move>(G);
+        d_sc = c.take<int32_t>(G);
+        d_pos = c.take<uint32_t>(G);
+        return c.off;
     };
-    hipError_t e;
-    // on cfg->device, on a stream of its own (as oaz_pure_mcts_search): the null stream is not waited for,
-    // and the calling thread's current device is restored on return
-    hipStream_t sm = nullptr;
-    char* buf = nullptr;
-    int prev_dev = -1;
-    if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-    if ((e = hipSetDevice(cfg->device)) != hipSuccess) fail(e, "set device");
-    else if ((e = hipStreamCreateWithFlags(&sm, hipStreamNonBlocking)) != hipSuccess) fail(e, "stream");
-    else if ((e = hipMalloc(reinterpret_cast<void**>(&buf), bytes)) != hipSuccess) fail(e, "alloc");
-    if (!rc) {
-        oaz_state* d_roots = reinterpret_cast<oaz_state*>(buf);
-        oaz_move* d_mv = reinterpret_cast<oaz_move*>(buf + o_mv);
-        int32_t* d_sc = reinterpret_cast<int32_t*>(buf + o_sc);
-        uint32_t* d_pos = reinterpret_cast<uint32_t*>(buf + o_pos);
-        std::vector<uint32_t> pos((size_t)G);
-        if ((e = hipMemcpyAsync(d_roots, roots, sizeof(oaz_state) * G, hipMemcpyHostToDevice, sm)) != hipSuccess)
-            fail(e, "upload");
-        if (!rc) {
-            hipLaunchKernelGGL(ab::k_alphabeta, dim3((G + ab::kGamesPerBlock - 1) / ab::kGamesPerBlock), dim3(ab::kThreads),
-                               lds_bytes, sm, d_roots, G, plies, d_mv, d_sc, d_pos);
-            if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(sm)) != hipSuccess) fail(e, "kernel");
+    // on cfg->device, on a stream of its own (as oaz_pure_mcts_search): the null stream is not waited for, and
+    // the calling thread's current device is restored on return. The stream is declared after the buffer: on
+    // every return it is waited for before the buffer is freed (and before `pos` goes).
+    OAZ_ON_DEVICE(cfg->device);
+    std::vector<uint32_t> pos((size_t)G);
+    DevBuf<char> buf;
+    Stream sm;
+    if (int rc = sm.create()) return rc;
+    if (int rc = buf.alloc(carve(Carver{nullptr}))) return rc;
+    carve(Carver{buf});
+    HIP_TRY(hipMemcpyAsync(d_roots, roots, sizeof(oaz_state) * G, hipMemcpyHostToDevice, sm));
+    hipLaunchKernelGGL(ab::k_alphabeta, dim3((G + ab::kGamesPerBlock - 1) / ab::kGamesPerBlock), dim3(ab::kThreads),
+                       lds_bytes, sm, d_roots, G, plies, d_mv, d_sc, d_pos);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(sm));
+    HIP_TRY(hipMemcpyAsync(out_move, d_mv, sizeof(oaz_move) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(out_score, d_sc, sizeof(int32_t) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(pos.data(), d_pos, sizeof(uint32_t) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipStreamSynchronize(sm));
+    if (stats)
+        for (int g = 0; g < G; ++g) {
+            stats->positions += pos[g];
+            if (pos[g] > stats->max_positions_per_root) stats->max_positions_per_root = pos[g];
+            stats->roots_without_move += out_move[g].from >= 25;
         }
-        if (!rc) {
-            (void)hipMemcpyAsync(out_move, d_mv, sizeof(oaz_move) * G, hipMemcpyDeviceToHost, sm);
-            (void)hipMemcpyAsync(out_score, d_sc, sizeof(int32_t) * G, hipMemcpyDeviceToHost, sm);
-            (void)hipMemcpyAsync(pos.data(), d_pos, sizeof(uint32_t) * G, hipMemcpyDeviceToHost, sm);
-            if ((e = hipStreamSynchronize(sm)) != hipSuccess) fail(e, "copy");
-        }
-        if (!rc && stats)
-            for (int g = 0; g < G; ++g) {
-                stats->positions += pos[g];
-                if (pos[g] > stats->max_positions_per_root) stats->max_positions_per_root = pos[g];
-                stats->roots_without_move += out_move[g].from >= 25;
-            }
-    }
-    if (sm) (void)hipStreamSynchronize(sm);
-    if (buf) (void)hipFree(buf);
-    if (sm) (void)hipStreamDestroy(sm);
-    if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
-    return rc;
+    return 0;
 }

@@ -71,12 +71,14 @@ int rccl_load() {
                                __FILE__, __LINE__);                                                      \
     } while (0)
 
+// The device resources are owning members (oaz_host.h), destroyed in reverse declaration order after
+// oaz_comm_destroy waited for the stream and destroyed the RCCL communicator: events, buffer, stream last.
 struct oaz_comm {
     ncclComm_t nc = nullptr;
     int rank = 0, world = 1, device = 0;
-    hipStream_t stream = nullptr;
-    uint64_t* d_counts = nullptr;  // [world] all-gathered sample counts
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // last all-gather: start, counts done, records done
+    Stream stream;
+    DevBuf<uint64_t> d_counts;  // [world] all-gathered sample counts
+    Event ev[3];                // last all-gather: start, counts done, records done
     oaz_comm_stats st{};
 };
 
@@ -92,30 +94,25 @@ extern "C" int oaz_comm_unique_id(oaz_comm_id* out) {
 extern "C" void oaz_comm_destroy(oaz_comm* c) {
     if (!c) return;
     DeviceScope dev_scope_(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    (void)c->stream.sync();
     if (c->nc) (void)g_rccl.comm_destroy(c->nc);
-    if (c->d_counts) (void)hipFree(c->d_counts);
-    for (auto ev : c->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
 static int comm_init(const oaz_comm_id* id, int rank, int world, int device, oaz_comm** out) {
     if (!id || world < 1 || rank < 0 || rank >= world) return oaz_set_err(OAZ_ERR_ARG, "comm_init: rank %d of %d", rank, world);
     if (int rc = rccl_load()) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return oaz_set_err(OAZ_ERR_NO_DEVICE, "comm_init: no HIP device");
-    if (device < 0 || device >= ndev) return oaz_set_err(OAZ_ERR_ARG, "comm_init: device %d of %d", device, ndev);
+    if (int rc = oaz_check_device("comm_init", device)) return rc;
     oaz_comm* c = new oaz_comm();
     *out = c;
     c->rank = rank;
     c->world = world;
     c->device = device;
     OAZ_ON_DEVICE(device);
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc((void**)&c->d_counts, (size_t)world * sizeof(uint64_t)));
-    for (auto& ev : c->ev) HIP_TRY(hipEventCreate(&ev));
+    if (int rc = c->stream.create()) return rc;
+    if (int rc = c->d_counts.alloc((size_t)world)) return rc;
+    for (auto& ev : c->ev)
+        if (int rc = ev.create(hipEventDefault)) return rc;
     ncclUniqueId uid;
     memcpy(uid.internal, id->internal, sizeof(uid.internal));
     NCCL_TRY(g_rccl.comm_init_rank(&c->nc, world, uid, rank));

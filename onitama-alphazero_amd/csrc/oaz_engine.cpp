@@ -169,30 +169,20 @@ extern "C" void oaz_hash_eval(const oaz_state* s, float policy[50], float* value
 }
 
 // ---- rules context (no engine needed) ----------------------------------------------------------
-struct Scratch {
-    void* p = nullptr;
-    size_t n = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= n) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        HIP_TRY(hipMalloc(&p, bytes));
-        n = bytes;
-        return 0;
-    }
-};
-
 // One context per device (stream + scratch buffers allocated on that device): the rules entry points run
 // on the calling thread's current device, so calls from threads on different GPUs never share buffers.
 struct RulesCtx {
     std::mutex mu;
     bool init = false;
-    hipStream_t stream = nullptr;
-    Scratch a, b, c, d;
+    Stream stream;
+    DevBuf<oaz_state> a;  // grow-only scratch: states,
+    DevBuf<uint32_t> b;   // move masks or input planes (4-byte words),
+    DevBuf<oaz_move> c;   // moves,
+    DevBuf<uint8_t> d;    // move counts or results
 };
 constexpr int kRulesMaxDevices = 64;
-static RulesCtx g_rules_dev[kRulesMaxDevices];
+// never deleted: no hipFree or hipStreamDestroy while the HIP runtime unloads at process exit (oaz_host.h)
+static RulesCtx* const g_rules_dev = new RulesCtx[kRulesMaxDevices];
 
 // The current device's context, locked for the caller (lk), its stream created on first use.
 static int rules_begin(RulesCtx** out, std::unique_lock<std::mutex>& lk) {
@@ -205,7 +195,7 @@ static int rules_begin(RulesCtx** out, std::unique_lock<std::mutex>& lk) {
     RulesCtx& r = g_rules_dev[dev];
     lk = std::unique_lock<std::mutex>(r.mu);
     if (!r.init) {
-        HIP_TRY(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
+        if (int rc = r.stream.create()) return rc;
         r.init = true;
     }
     *out = &r;
@@ -219,16 +209,16 @@ extern "C" int oaz_movegen(const oaz_state* s, int n, uint32_t* masks, oaz_move*
     std::unique_lock<std::mutex> lk;
     if (int rc = rules_begin(&R, lk)) return rc;
     hipStream_t st = R->stream;
-    if (int rc = R->a.ensure((size_t)n * sizeof(oaz_state))) return rc;
-    if (int rc = R->b.ensure((size_t)n * 50 * 4)) return rc;
-    if (int rc = R->c.ensure((size_t)n * OAZ_MAX_MOVES * sizeof(oaz_move))) return rc;
-    if (int rc = R->d.ensure((size_t)n)) return rc;
-    HIP_TRY(hipMemcpyAsync(R->a.p, s, (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_movegen((oaz_state*)R->a.p, n, masks ? (uint32_t*)R->b.p : nullptr,
-                           moves ? (oaz_move*)R->c.p : nullptr, counts ? (uint8_t*)R->d.p : nullptr, st));
-    if (masks) HIP_TRY(hipMemcpyAsync(masks, R->b.p, (size_t)n * 50 * 4, hipMemcpyDeviceToHost, st));
-    if (moves) HIP_TRY(hipMemcpyAsync(moves, R->c.p, (size_t)n * OAZ_MAX_MOVES * sizeof(oaz_move), hipMemcpyDeviceToHost, st));
-    if (counts) HIP_TRY(hipMemcpyAsync(counts, R->d.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    if (int rc = R->a.reserve((size_t)n)) return rc;
+    if (int rc = R->b.reserve((size_t)n * 50)) return rc;
+    if (int rc = R->c.reserve((size_t)n * OAZ_MAX_MOVES)) return rc;
+    if (int rc = R->d.reserve((size_t)n)) return rc;
+    HIP_TRY(hipMemcpyAsync(R->a, s, (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_movegen(R->a, n, masks ? R->b.get() : nullptr, moves ? R->c.get() : nullptr,
+                           counts ? R->d.get() : nullptr, st));
+    if (masks) HIP_TRY(hipMemcpyAsync(masks, R->b, (size_t)n * 50 * 4, hipMemcpyDeviceToHost, st));
+    if (moves) HIP_TRY(hipMemcpyAsync(moves, R->c, (size_t)n * OAZ_MAX_MOVES * sizeof(oaz_move), hipMemcpyDeviceToHost, st));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, R->d, (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
@@ -243,14 +233,14 @@ extern "C" int oaz_step(oaz_state* s, const oaz_move* mv, int n, uint8_t* result
     std::unique_lock<std::mutex> lk;
     if (int rc = rules_begin(&R, lk)) return rc;
     hipStream_t st = R->stream;
-    if (int rc = R->a.ensure((size_t)n * sizeof(oaz_state))) return rc;
-    if (int rc = R->c.ensure((size_t)n * sizeof(oaz_move))) return rc;
-    if (int rc = R->d.ensure((size_t)n)) return rc;
-    HIP_TRY(hipMemcpyAsync(R->a.p, s, (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(R->c.p, mv, (size_t)n * sizeof(oaz_move), hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_step((oaz_state*)R->a.p, (const oaz_move*)R->c.p, n, (uint8_t*)R->d.p, st));
-    HIP_TRY(hipMemcpyAsync(s, R->a.p, (size_t)n * sizeof(oaz_state), hipMemcpyDeviceToHost, st));
-    if (results) HIP_TRY(hipMemcpyAsync(results, R->d.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    if (int rc = R->a.reserve((size_t)n)) return rc;
+    if (int rc = R->c.reserve((size_t)n)) return rc;
+    if (int rc = R->d.reserve((size_t)n)) return rc;
+    HIP_TRY(hipMemcpyAsync(R->a, s, (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(R->c, mv, (size_t)n * sizeof(oaz_move), hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_step(R->a, R->c, n, R->d, st));
+    HIP_TRY(hipMemcpyAsync(s, R->a, (size_t)n * sizeof(oaz_state), hipMemcpyDeviceToHost, st));
+    if (results) HIP_TRY(hipMemcpyAsync(results, R->d, (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
@@ -262,11 +252,11 @@ extern "C" int oaz_current_state(const oaz_state* s, int n, uint8_t* results) {
     std::unique_lock<std::mutex> lk;
     if (int rc = rules_begin(&R, lk)) return rc;
     hipStream_t st = R->stream;
-    if (int rc = R->a.ensure((size_t)n * sizeof(oaz_state))) return rc;
-    if (int rc = R->d.ensure((size_t)n)) return rc;
-    HIP_TRY(hipMemcpyAsync(R->a.p, s, (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_current_state((const oaz_state*)R->a.p, n, (uint8_t*)R->d.p, st));
-    HIP_TRY(hipMemcpyAsync(results, R->d.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    if (int rc = R->a.reserve((size_t)n)) return rc;
+    if (int rc = R->d.reserve((size_t)n)) return rc;
+    HIP_TRY(hipMemcpyAsync(R->a, s, (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_current_state(R->a, n, R->d, st));
+    HIP_TRY(hipMemcpyAsync(results, R->d, (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
@@ -278,11 +268,11 @@ extern "C" int oaz_encode(const oaz_state* s, int n, float* planes) {
     std::unique_lock<std::mutex> lk;
     if (int rc = rules_begin(&R, lk)) return rc;
     hipStream_t st = R->stream;
-    if (int rc = R->a.ensure((size_t)n * sizeof(oaz_state))) return rc;
-    if (int rc = R->b.ensure((size_t)n * 525 * 4)) return rc;
-    HIP_TRY(hipMemcpyAsync(R->a.p, s, (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_encode((const oaz_state*)R->a.p, n, (float*)R->b.p, st));
-    HIP_TRY(hipMemcpyAsync(planes, R->b.p, (size_t)n * 525 * 4, hipMemcpyDeviceToHost, st));
+    if (int rc = R->a.reserve((size_t)n)) return rc;
+    if (int rc = R->b.reserve((size_t)n * 525)) return rc;
+    HIP_TRY(hipMemcpyAsync(R->a, s, (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_encode(R->a, n, (float*)R->b.get(), st));
+    HIP_TRY(hipMemcpyAsync(planes, R->b, (size_t)n * 525 * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
@@ -293,88 +283,78 @@ constexpr int kMaxParts = 4;  // run_sims: game parts, each on its own stream (o
 struct TimedLaunch {
     int kind;  // 0 select, 1 nn, 2 expand, 3 finalize, 4 root noise (second stream), 5 leaf compaction,
                // 6 expand/backup + next select (fused)
-    hipEvent_t a, b;
+    Event a, b;
     uint32_t samples;
 };
 
+// The device resources are owning members (oaz_host.h), destroyed in reverse declaration order after
+// oaz_destroy synchronised the streams: events (declared last) first, then the buffers, the streams
+// (declared first) last. Keep that order when adding a member.
 struct oaz_engine {
     oaz_config cfg;
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;       // root-noise producer, overlaps the NN kernel
-    int cus = 256;                       // compute units of the device (leaf-compaction threshold)
-    hipStream_t stream3[kMaxParts - 1] = {nullptr, nullptr, nullptr};  // the streams of game parts 1.. (oaz_config.parts)
-    hipEvent_t ev_join = nullptr, ev_part[kMaxParts] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_ready[2] = {nullptr, nullptr};
-    hipEvent_t ev_consumed[2][kMaxParts] = {};  // noise ring slot done with, per game part
-    noise_t* noise = nullptr;            // [2][noise_chunk][G][kNoiseStride] (f64 draws; f32 in an OAZ_NOISE_F32 build)
+    Stream stream;
+    Stream stream2;                      // root-noise producer, overlaps the NN kernel
+    Stream stream3[kMaxParts - 1];       // the streams of game parts 1.. (oaz_config.parts)
+    int cus = 256;                      // compute units of the device (leaf-compaction threshold)
+    DevBuf<noise_t> noise;               // [2][noise_chunk][G][kNoiseStride] (f64 draws; f32 in an OAZ_NOISE_F32 build)
     uint32_t noise_chunk = 16;           // simulations per noise ring slot (noise_chunk_for)
     uint32_t G = 0, cap = 0, pathcap = 0, hcap = 0, out_cap = 0;
     int32_t sims_cap = 0;                // cfg.sims at creation: trees and paths are sized for it
     // trees
-    oaz_node* nodes = nullptr;
-    uint32_t *n_nodes = nullptr, *path = nullptr, *depth = nullptr, *leaf = nullptr;
-    oaz_state* leaf_state = nullptr;
-    uint64_t* stats = nullptr;
-    uint64_t* stats_sum = nullptr;
-    double* sqrt_tab = nullptr;
-    float *policy = nullptr, *value = nullptr;  // evaluations by compacted row (TreeView::slot)
-    uint8_t* need = nullptr;                    // leaf compaction (oaz_kernels.h TreeView)
-    uint32_t *slot = nullptr, *bcnt = nullptr;
-    oaz_state* cstate = nullptr;
-    float* weights = nullptr;
+    DevBuf<oaz_node> nodes;
+    DevBuf<uint32_t> n_nodes, path, depth, leaf;
+    DevBuf<oaz_state> leaf_state;
+    DevBuf<uint64_t> stats, stats_sum;
+    DevBuf<double> sqrt_tab;
+    DevBuf<float> policy, value;         // evaluations by compacted row (TreeView::slot)
+    DevBuf<uint8_t> need;                // leaf compaction (oaz_kernels.h TreeView)
+    DevBuf<uint32_t> slot, bcnt;
+    DevBuf<oaz_state> cstate;
+    DevBuf<float> weights;
     bool have_weights = false;
-    unsigned long long* nn_fallback = nullptr;  // OAZ_FP32_SPLIT16: tiles recomputed by k_nn_x6 (fp16 range)
+    DevBuf<unsigned long long> nn_fallback;  // OAZ_FP32_SPLIT16: tiles recomputed by k_nn_x6 (fp16 range)
     // search mode
-    oaz_state* s_roots = nullptr;
-    oaz_move* s_move = nullptr;
-    float* s_pi = nullptr;
-    float* s_rootv = nullptr;
-    float* s_rootp = nullptr;
+    DevBuf<oaz_state> s_roots;
+    DevBuf<oaz_move> s_move;
+    DevBuf<float> s_pi, s_rootv, s_rootp;
     uint32_t search_calls = 0;
     uint32_t last_sims = 0;  // simulations per game of the last run_sims (Q7 budget: may be < cfg.sims)
     // Q7 on the device (the one-launch searches): the deadline on the device clock, each game's simulation
     // count (last_sims_dev: the last run_sims wrote them for its last_G games; last_sims is then their maximum)
-    uint64_t* deadline = nullptr;
-    uint32_t* sims_run = nullptr;
+    DevBuf<uint64_t> deadline;
+    DevBuf<uint32_t> sims_run;
     int wall_khz = 0;  // hipDeviceAttributeWallClockRate (kHz)
     bool last_sims_dev = false;
     bool deadline_armed = false;  // begin_budget launched k_deadline_start for the current search / ply
     double t_search0 = 0.0;       // host clock at the start of the current search / ply (0: no budget)
     uint32_t last_G = 0;
     std::vector<uint32_t> sims_host;  // per-game counts of the last device-budgeted run (empty: all last_sims)
-    uint32_t* s_ply = nullptr;
+    DevBuf<uint32_t> s_ply;
     // self-play
-    oaz_state* root = nullptr;
-    uint32_t *ply = nullptr, *seq = nullptr;
-    uint64_t* game_id = nullptr;
-    uint8_t* active = nullptr;
-    oaz_sample* hist = nullptr;
-    oaz_sample* out = nullptr;
-    unsigned long long* out_count = nullptr;
-    uint32_t* fin = nullptr;      // SlotView::fin / fin_pos (records of the games that ended in a ply)
-    uint64_t* fin_pos = nullptr;
+    DevBuf<oaz_state> root;
+    DevBuf<uint32_t> ply, seq;
+    DevBuf<uint64_t> game_id;
+    DevBuf<uint8_t> active;
+    DevBuf<oaz_sample> hist, out;
+    DevBuf<unsigned long long> out_count;
+    DevBuf<uint32_t> fin;      // SlotView::fin / fin_pos (records of the games that ended in a ply)
+    DevBuf<uint64_t> fin_pos;
     unsigned long long out_read = 0;  // samples already handed out
     bool selfplay_ready = false;
     uint64_t quota = 0;
+    // events (after the buffers: destroyed before them)
+    Event ev_join, ev_part[kMaxParts];   // (ev_part[0] is never made: part 0 runs on `stream`)
+    Event ev_ready[2];
+    Event ev_consumed[2][kMaxParts];     // noise ring slot done with, per game part
     // timing
     bool timing = false;
     int timing_every = 1;     // time the kernels of every N-th simulation step (events cost ~2 % each)
     bool timing_skip = false; // run_sims: this simulation step is not sampled
     std::vector<TimedLaunch> pending;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     oaz_kernel_times times{};
 };
-
-template <class T>
-static int dalloc(T** p, size_t count) {
-    HIP_TRY(hipMalloc((void**)p, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
-    return 0;
-}
-
-static void dfree(void* p) {
-    if (p) (void)hipFree(p);
-}
 
 static TreeView tree_view(oaz_engine* e, uint32_t G) {
     TreeView t;
@@ -432,14 +412,15 @@ static SearchParams search_params(const oaz_engine* e) {
     return p;
 }
 
-static hipEvent_t ev_get(oaz_engine* e) {
-    if (!e->pool.empty()) {
-        hipEvent_t ev = e->pool.back();
-        e->pool.pop_back();
+// A timing event from the pool, or a new one (one that could not be made fails its first hipEventRecord).
+static Event ev_get(oaz_engine* e) {
+    if (e->pool.empty()) {
+        Event ev;
+        (void)ev.create(hipEventDefault);
         return ev;
     }
-    hipEvent_t ev = nullptr;
-    (void)hipEventCreate(&ev);
+    Event ev = std::move(e->pool.back());
+    e->pool.pop_back();
     return ev;
 }
 
@@ -486,11 +467,24 @@ static int resolve_pending(oaz_engine* e) {
         i = j;
     }
     for (auto& p : e->pending) {
-        e->pool.push_back(p.a);
-        e->pool.push_back(p.b);
+        e->pool.push_back(std::move(p.a));
+        e->pool.push_back(std::move(p.b));
     }
     e->pending.clear();
     return 0;
+}
+
+// Waits for all the engine's streams.
+static int sync_streams(oaz_engine* e) {
+    HIP_TRY(e->stream.sync());
+    HIP_TRY(e->stream2.sync());
+    for (auto& s3 : e->stream3) HIP_TRY(s3.sync());
+    return 0;
+}
+
+static int resolve_timing(oaz_engine* e) {
+    if (int rc = sync_streams(e)) return rc;
+    return resolve_pending(e);
 }
 
 template <class F>
@@ -500,57 +494,89 @@ static int timed(oaz_engine* e, int kind, uint32_t samples, F&& launch, hipStrea
         HIP_TRY(launch());
         return 0;
     }
-    TimedLaunch t;
-    t.kind = kind;
-    t.samples = samples;
-    t.a = ev_get(e);
-    t.b = ev_get(e);
+    TimedLaunch t{kind, ev_get(e), ev_get(e), samples};
     HIP_TRY(hipEventRecord(t.a, st));
     HIP_TRY(launch());
     HIP_TRY(hipEventRecord(t.b, st));
-    e->pending.push_back(t);
-    if (e->pending.size() > 4096) {  // resolve periodically to bound the pool
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream2));
-        for (auto s3 : e->stream3) HIP_TRY(hipStreamSynchronize(s3));
-        return resolve_pending(e);
-    }
+    e->pending.push_back(std::move(t));
+    if (e->pending.size() > 4096) return resolve_timing(e);  // resolve periodically to bound the pool
     return 0;
 }
 
-extern "C" oaz_engine* oaz_create(const oaz_config* cfg, int device) {
-    if (!cfg) {
-        oaz_set_err(OAZ_ERR_ARG, "create: null config");
-        return nullptr;
-    }
-    if (cfg->channels != 64 || cfg->in_planes != 21) {
-        oaz_set_err(OAZ_ERR_ARG, "create: only channels=64, in_planes=21 are supported");
-        return nullptr;
-    }
+// The argument checks of oaz_create.
+static int create_check(const oaz_config* cfg, int device) {
+    if (!cfg) return oaz_set_err(OAZ_ERR_ARG, "create: null config");
+    if (cfg->channels != 64 || cfg->in_planes != 21)
+        return oaz_set_err(OAZ_ERR_ARG, "create: only channels=64, in_planes=21 are supported");
     if (cfg->blocks < 0 || cfg->blocks > 64 || cfg->sims < 1 || cfg->sims > 65535 || cfg->games < 1 ||
         cfg->max_plies < 0 || cfg->max_plies > 100000 || cfg->compact < 0 || cfg->compact > 2 || cfg->search_time_ns < 0 ||
         cfg->step_kernels < 0 || cfg->step_kernels > 1 || cfg->world < 0 || cfg->rank < 0 ||
         cfg->rank >= (cfg->world > 0 ? cfg->world : 1) ||
         (uint64_t)cfg->games * ((uint64_t)cfg->sims + 1) >= (1ull << 32) ||  // 32-bit path offsets (k_select_seg)
         (uint64_t)cfg->games * kNoiseStride * sizeof(noise_t) >= (1ull << 31) ||  // 32-bit noise offsets (root_noise_pairs)
-        (cfg->parts != 0 && cfg->parts != 1 && cfg->parts != 2 && cfg->parts != 4)) {
-        oaz_set_err(OAZ_ERR_ARG, "create: config out of range");
-        return nullptr;
-    }
+        (cfg->parts != 0 && cfg->parts != 1 && cfg->parts != 2 && cfg->parts != 4))
+        return oaz_set_err(OAZ_ERR_ARG, "create: config out of range");
     if (cfg->precision != OAZ_FP32 && cfg->precision != OAZ_BF16 && cfg->precision != OAZ_FP32_SPLIT &&
-        cfg->precision != OAZ_FP32_SPLIT16) {
-        oaz_set_err(OAZ_ERR_ARG, "create: precision must be OAZ_FP32, OAZ_BF16, OAZ_FP32_SPLIT or OAZ_FP32_SPLIT16");
-        return nullptr;
+        cfg->precision != OAZ_FP32_SPLIT16)
+        return oaz_set_err(OAZ_ERR_ARG, "create: precision must be OAZ_FP32, OAZ_BF16, OAZ_FP32_SPLIT or OAZ_FP32_SPLIT16");
+    return oaz_check_device("create", device);
+}
+
+// The device side of oaz_create: streams, events, buffers and their first contents. On an error the engine is
+// partly built; oaz_destroy takes it as it is (a member not made yet holds nothing).
+static int engine_init(oaz_engine* e) {
+    const oaz_config* cfg = &e->cfg;
+    OAZ_ON_DEVICE(e->device);  // the caller's current device is restored on return
+    if (e->stream.create() || e->stream2.create() || e->ev_join.create()) return OAZ_ERR_HIP;
+    for (int i = 0; i < kMaxParts - 1; ++i)
+        if (e->stream3[i].create() || e->ev_part[i + 1].create()) return OAZ_ERR_HIP;
+    for (int i = 0; i < 2; ++i) {
+        if (e->ev_ready[i].create()) return OAZ_ERR_HIP;
+        for (auto& ev : e->ev_consumed[i])
+            if (ev.create()) return OAZ_ERR_HIP;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        oaz_set_err(OAZ_ERR_NO_DEVICE, "create: no HIP device visible");
-        return nullptr;
+    if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || e->cus < 1)
+        e->cus = 256;
+    if (hipDeviceGetAttribute(&e->wall_khz, hipDeviceAttributeWallClockRate, e->device) != hipSuccess) e->wall_khz = 0;
+    const size_t G = e->G;
+    e->noise_chunk = noise_chunk_for(e);
+    if (e->nodes.alloc(G * e->cap) || e->n_nodes.alloc(G) || e->path.alloc(G * e->pathcap) || e->depth.alloc(G) ||
+        e->leaf.alloc(G) || e->leaf_state.alloc(G) || e->stats.alloc(G * GS_COUNT) || e->stats_sum.alloc(GS_COUNT) ||
+        e->sqrt_tab.alloc((size_t)cfg->sims + 2) || e->policy.alloc(G * 50) || e->value.alloc(G) || e->need.alloc(G) ||
+        e->slot.alloc(G) || e->cstate.alloc(G + 16) || e->bcnt.alloc((size_t)buckets_of((uint32_t)G) + kMaxParts) ||
+        e->weights.alloc(nn_device_floats(cfg->blocks, cfg->precision)) || e->s_roots.alloc(G) || e->s_move.alloc(G) ||
+        e->s_pi.alloc(G * 50) || e->s_rootv.alloc(G) || e->s_rootp.alloc(G * 50) || e->s_ply.alloc(G) ||
+        e->root.alloc(G) || e->ply.alloc(G) || e->seq.alloc(G) || e->game_id.alloc(G) || e->active.alloc(G) ||
+        e->hist.alloc(G * e->hcap) || e->out.alloc(e->out_cap) || e->out_count.alloc(1) || e->nn_fallback.alloc(1) ||
+        e->deadline.alloc(1) || e->sims_run.alloc(G) || e->fin.alloc(G) || e->fin_pos.alloc(G) ||
+        (cfg->train_noise && e->noise.alloc(2 * (size_t)e->noise_chunk * G * kNoiseStride)))
+        return OAZ_ERR_HIP;  // (alloc's HIP_TRY recorded the call and the HIP error)
+    // sqrt((double)n) from the host libm (IEEE correctly rounded), so device PUCT = oracle PUCT
+    std::vector<double> tab((size_t)cfg->sims + 2);
+    for (size_t i = 0; i < tab.size(); ++i) tab[i] = sqrt((double)i);
+    // on the engine's own stream, waited for: its streams do not synchronise with the null stream, a null-stream
+    // hipMemset returns before it ran and a pageable hipMemcpy before its DMA landed, so the first kernels could
+    // otherwise read these buffers early (seen with several engines created concurrently on one GPU)
+    hipStream_t s0 = e->stream;
+    HIP_TRY(hipMemcpyAsync(e->sqrt_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, s0));
+    HIP_TRY(hipMemsetAsync(e->stats, 0, G * GS_COUNT * sizeof(uint64_t), s0));
+    HIP_TRY(hipMemsetAsync(e->out_count, 0, sizeof(unsigned long long), s0));
+    HIP_TRY(hipMemsetAsync(e->nn_fallback, 0, sizeof(unsigned long long), s0));
+    HIP_TRY(hipMemsetAsync(e->active, 0, G, s0));
+    HIP_TRY(hipMemsetAsync(e->need, 0, G, s0));
+    HIP_TRY(hipMemsetAsync(e->slot, 0, G * sizeof(uint32_t), s0));
+    HIP_TRY(hipMemsetAsync(e->cstate, 0, (G + 16) * sizeof(oaz_state), s0));
+    HIP_TRY(hipStreamSynchronize(s0));
+    if (cfg->evaluator == OAZ_EVAL_NN) {  // random-init weights until oaz_load_weights
+        std::vector<float> w(oaz_weight_count(cfg->blocks, 64, 21));
+        if (int rc = oaz_random_weights(0, cfg->blocks, w.data(), w.size())) return rc;
+        if (int rc = oaz_load_weights(e, w.data(), w.size())) return rc;
     }
-    if (device < 0 || device >= ndev) {
-        oaz_set_err(OAZ_ERR_ARG, "create: device %d out of range (%d visible)", device, ndev);
-        return nullptr;
-    }
+    return 0;
+}
+
+extern "C" oaz_engine* oaz_create(const oaz_config* cfg, int device) {
+    if (create_check(cfg, device)) return nullptr;
     oaz_engine* e = new oaz_engine();
     e->cfg = *cfg;
     e->device = device;
@@ -560,113 +586,23 @@ extern "C" oaz_engine* oaz_create(const oaz_config* cfg, int device) {
     e->pathcap = (uint32_t)cfg->sims + 1;               // depth grows by <= 1 per playout
     e->hcap = (uint32_t)cfg->max_plies + 2;             // train.rs:74-79 cut after max_plies+2 plies
     e->out_cap = cfg->sample_capacity > 0 ? (uint32_t)cfg->sample_capacity : e->G * 64u;
-    auto fail = [&](void) -> oaz_engine* {
-        std::string msg = g_err;
+    if (engine_init(e)) {  // the one failure exit: the partly built engine goes, the error text stays
+        const std::string msg = g_err;
         oaz_destroy(e);
         g_err = msg;
         return nullptr;
-    };
-    DeviceScope dev_scope_(device);  // the caller's current device is restored on return
-    if (dev_scope_.rc != hipSuccess) {
-        oaz_set_err(OAZ_ERR_HIP, "hipSetDevice(%d) failed", device);
-        return fail();
-    }
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess) {
-        oaz_set_err(OAZ_ERR_HIP, "stream create failed");
-        return fail();
-    }
-    for (int i = 0; i < kMaxParts - 1; ++i)
-        if (hipStreamCreateWithFlags(&e->stream3[i], hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_part[i + 1], hipEventDisableTiming) != hipSuccess) {
-            oaz_set_err(OAZ_ERR_HIP, "stream create failed");
-            return fail();
-        }
-    for (int i = 0; i < 2; ++i)
-        if (hipEventCreateWithFlags(&e->ev_ready[i], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_consumed[i][0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_consumed[i][1], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_consumed[i][2], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&e->ev_consumed[i][3], hipEventDisableTiming) != hipSuccess) {
-            oaz_set_err(OAZ_ERR_HIP, "event create failed");
-            return fail();
-        }
-    if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || e->cus < 1)
-        e->cus = 256;
-    if (hipDeviceGetAttribute(&e->wall_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess) e->wall_khz = 0;
-    const size_t G = e->G;
-    e->noise_chunk = noise_chunk_for(e);
-    if (dalloc(&e->nodes, G * e->cap) || dalloc(&e->n_nodes, G) || dalloc(&e->path, G * e->pathcap) ||
-        dalloc(&e->depth, G) || dalloc(&e->leaf, G) || dalloc(&e->leaf_state, G) ||
-        dalloc(&e->stats, G * GS_COUNT) || dalloc(&e->stats_sum, (size_t)GS_COUNT) ||
-        dalloc(&e->sqrt_tab, (size_t)cfg->sims + 2) || dalloc(&e->policy, G * 50) ||
-        dalloc(&e->value, G) || dalloc(&e->need, G) || dalloc(&e->slot, G) || dalloc(&e->cstate, G + 16) ||
-        dalloc(&e->bcnt, (size_t)buckets_of((uint32_t)G) + kMaxParts) || dalloc(&e->weights, nn_device_floats(cfg->blocks, cfg->precision)) ||
-        dalloc(&e->s_roots, G) || dalloc(&e->s_move, G) || dalloc(&e->s_pi, G * 50) ||
-        dalloc(&e->s_rootv, G) || dalloc(&e->s_rootp, G * 50) || dalloc(&e->s_ply, G) ||
-        dalloc(&e->root, G) || dalloc(&e->ply, G) || dalloc(&e->seq, G) ||
-        dalloc(&e->game_id, G) || dalloc(&e->active, G) || dalloc(&e->hist, G * e->hcap) ||
-        dalloc(&e->out, (size_t)e->out_cap) || dalloc(&e->out_count, (size_t)1) || dalloc(&e->nn_fallback, (size_t)1) ||
-        dalloc(&e->deadline, (size_t)1) || dalloc(&e->sims_run, G) || dalloc(&e->fin, G) || dalloc(&e->fin_pos, G) ||
-        (cfg->train_noise && dalloc(&e->noise, 2 * (size_t)e->noise_chunk * G * kNoiseStride)))
-        return fail();
-    // sqrt((double)n) from the host libm (IEEE correctly rounded), so device PUCT = oracle PUCT
-    std::vector<double> tab((size_t)cfg->sims + 2);
-    for (size_t i = 0; i < tab.size(); ++i) tab[i] = sqrt((double)i);
-    // on the engine's own stream, waited for: its streams do not synchronise with the null stream, a null-stream
-    // hipMemset returns before it ran and a pageable hipMemcpy before its DMA landed, so the first kernels could
-    // otherwise read these buffers early (seen with several engines created concurrently on one GPU)
-    hipStream_t s0 = e->stream;
-    if (hipMemcpyAsync(e->sqrt_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, s0) != hipSuccess ||
-        hipMemsetAsync(e->stats, 0, G * GS_COUNT * sizeof(uint64_t), s0) != hipSuccess ||
-        hipMemsetAsync(e->out_count, 0, sizeof(unsigned long long), s0) != hipSuccess ||
-        hipMemsetAsync(e->nn_fallback, 0, sizeof(unsigned long long), s0) != hipSuccess ||
-        hipMemsetAsync(e->active, 0, G, s0) != hipSuccess || hipMemsetAsync(e->need, 0, G, s0) != hipSuccess ||
-        hipMemsetAsync(e->slot, 0, G * sizeof(uint32_t), s0) != hipSuccess ||
-        hipMemsetAsync(e->cstate, 0, (G + 16) * sizeof(oaz_state), s0) != hipSuccess ||
-        hipStreamSynchronize(s0) != hipSuccess) {
-        oaz_set_err(OAZ_ERR_HIP, "create: init copies failed");
-        return fail();
-    }
-    if (cfg->evaluator == OAZ_EVAL_NN) {  // random-init weights until oaz_load_weights
-        std::vector<float> w(oaz_weight_count(cfg->blocks, 64, 21));
-        if (oaz_random_weights(0, cfg->blocks, w.data(), w.size()) || oaz_load_weights(e, w.data(), w.size()))
-            return fail();
     }
     return e;
 }
 
+// On the engine's device: wait for its streams, then `delete` destroys the members (events, buffers, streams
+// last: the declaration order of oaz_engine), the timing events in `pending` and `pool` among them.
 extern "C" void oaz_destroy(oaz_engine* e) {
     if (!e) return;
     DeviceScope dev_scope_(e->device);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    if (e->stream2) (void)hipStreamSynchronize(e->stream2);
-    for (auto s3 : e->stream3)
-        if (s3) (void)hipStreamSynchronize(s3);
-    for (auto ev : e->ev_part)
-        if (ev) (void)hipEventDestroy(ev);
-    for (int i = 0; i < 2; ++i) {
-        if (e->ev_ready[i]) (void)hipEventDestroy(e->ev_ready[i]);
-        for (auto ev : e->ev_consumed[i])
-            if (ev) (void)hipEventDestroy(ev);
-    }
-    if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    for (auto& p : e->pending) {
-        (void)hipEventDestroy(p.a);
-        (void)hipEventDestroy(p.b);
-    }
-    for (auto ev : e->pool) (void)hipEventDestroy(ev);
-    void* ptrs[] = {e->nodes, e->n_nodes, e->path, e->depth, e->leaf, e->leaf_state, e->stats,
-                    e->stats_sum, e->sqrt_tab, e->policy, e->value, e->weights, e->s_roots,
-                    e->s_move, e->s_pi, e->s_rootv, e->s_rootp, e->s_ply, e->root, e->ply,
-                    e->seq, e->game_id, e->active, e->hist, e->out, e->out_count, e->noise, e->nn_fallback,
-                    e->need, e->slot, e->cstate, e->bcnt, e->deadline, e->sims_run, e->fin, e->fin_pos};
-    for (void* p : ptrs) dfree(p);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    if (e->stream2) (void)hipStreamDestroy(e->stream2);
-    for (auto s3 : e->stream3)
-        if (s3) (void)hipStreamDestroy(s3);
+    (void)e->stream.sync();
+    (void)e->stream2.sync();
+    for (auto& s3 : e->stream3) (void)s3.sync();
     delete e;
 }
 
@@ -679,7 +615,7 @@ extern "C" int oaz_set_search_params(oaz_engine* e, int sims, double c_puct, int
     if (train_noise && !e->noise) {  // the engine was made without root noise: its ring comes now
         OAZ_ON_DEVICE(e->device);
         HIP_TRY(hipStreamSynchronize(e->stream));
-        if (dalloc(&e->noise, 2 * (size_t)e->noise_chunk * e->G * kNoiseStride)) return OAZ_ERR_HIP;
+        if (int rc = e->noise.alloc(2 * (size_t)e->noise_chunk * e->G * kNoiseStride)) return rc;
     }
     e->cfg.sims = sims;
     e->cfg.c_puct = c_puct;
@@ -752,10 +688,7 @@ extern "C" int oaz_load_weights(oaz_engine* e, const float* blob, size_t n) {
 extern "C" int oaz_sync(oaz_engine* e) {
     if (!e) return oaz_set_err(OAZ_ERR_ARG, "sync: null");
     OAZ_ON_DEVICE(e->device);
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream2));
-    for (auto s3 : e->stream3) HIP_TRY(hipStreamSynchronize(s3));
-    return 0;
+    return sync_streams(e);
 }
 
 extern "C" int oaz_set_timing(oaz_engine* e, int enable) {
@@ -764,13 +697,6 @@ extern "C" int oaz_set_timing(oaz_engine* e, int enable) {
     e->timing = enable != 0;
     e->timing_every = enable > 1 ? enable : 1;
     return 0;
-}
-
-static int resolve_timing(oaz_engine* e) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream2));
-    for (auto s3 : e->stream3) HIP_TRY(hipStreamSynchronize(s3));
-    return resolve_pending(e);
 }
 
 extern "C" int oaz_kernel_times_get(oaz_engine* e, oaz_kernel_times* out) {
@@ -853,13 +779,24 @@ static bool compact_leaves(const oaz_engine* e, uint32_t G) {
     return e->cfg.compact == 1 || (e->cfg.compact == 2 && G >= 12u * 16u * (uint32_t)e->cus);
 }
 
+// What both one-launch searches (oaz_search_lat.hip) need: the segmented tree kernels they are built from, every
+// leaf evaluated in place, and an evaluator they contain (HASH, or the fp16x3 network).
+static bool one_launch_search(const oaz_engine* e, uint32_t G) {
+    return e->cfg.step_kernels == 0 && !compact_leaves(e, G) &&
+           (e->cfg.evaluator == OAZ_EVAL_HASH || e->cfg.precision == OAZ_FP32_SPLIT16) && tree_seg_kernels();
+}
+
 // A search of G games runs as k_search_grp launches (16 games per workgroup, up to one round of workgroups,
 // one launch per root-noise chunk) instead of the per-simulation-step launches. Everything it depends on is
 // fixed at creation except G (any G below a qualifying engine's qualifies as well).
 static bool grp_search(const oaz_engine* e, uint32_t G) {
-    const bool hash = e->cfg.evaluator == OAZ_EVAL_HASH;
-    return e->cfg.step_kernels == 0 && !compact_leaves(e, G) && (G + 15) / 16 <= (uint32_t)e->cus &&
-           (hash || e->cfg.precision == OAZ_FP32_SPLIT16) && tree_seg_kernels();
+    return one_launch_search(e, G) && (G + 15) / 16 <= (uint32_t)e->cus;
+}
+
+// k_search_lat: a workgroup per game runs all its simulations in one launch, when the per-step loop would
+// launch one NN workgroup per game anyway and nothing needs a second stream (the root noise) between steps.
+static bool lat_search(const oaz_engine* e, uint32_t G, bool noise) {
+    return one_launch_search(e, G) && !noise && G <= (uint32_t)e->cus;
 }
 
 // Simulations per root-noise ring slot. An engine whose searches run as k_search_grp: every chunk is one
@@ -976,15 +913,11 @@ static int run_sims_body(oaz_engine* e, const TreeView& t, const oaz_state* root
         e->last_sims_dev = true;
         return 0;
     };
-    uint64_t* const dl = budget_ns > 0 ? e->deadline : nullptr;
-    uint32_t* const sr = budget_ns > 0 ? e->sims_run : nullptr;
+    uint64_t* const dl = budget_ns > 0 ? e->deadline.get() : nullptr;
+    uint32_t* const sr = budget_ns > 0 ? e->sims_run.get() : nullptr;
     const bool noise = e->cfg.train_noise && e->noise;
-    // the one-launch search (oaz_search_lat.hip): a workgroup per game runs all its simulations, when the
-    // per-step loop would launch one NN workgroup per game anyway and nothing needs the host or a second
-    // stream between simulation steps
     const bool hash = e->cfg.evaluator == OAZ_EVAL_HASH;
-    if (e->cfg.step_kernels == 0 && !noise && !compact_leaves(e, t.G) && t.G <= (uint32_t)e->cus &&
-        (hash || e->cfg.precision == OAZ_FP32_SPLIT16) && tree_seg_kernels()) {
+    if (lat_search(e, t.G, noise)) {
         const NNView w = nn_view(e, nullptr);
         TreeView tl = t;  // rows = game ids (no compaction arrays)
         tl.need = nullptr;
@@ -1273,14 +1206,36 @@ extern "C" int oaz_selfplay_step(oaz_engine* e, int moves) {
     return 0;
 }
 
+// How many samples are ready: of the *avail records in the buffer after the engine stream's work so far (the
+// device's counter runs past out_cap when records were dropped), those not handed out yet.
+static int samples_ready(oaz_engine* e, size_t* ready, unsigned long long* avail) {
+    unsigned long long cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, e->out_count, sizeof(cnt), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *avail = cnt < e->out_cap ? cnt : e->out_cap;
+    *ready = *avail > e->out_read ? (size_t)(*avail - e->out_read) : 0;
+    return 0;
+}
+
+// Advances the read cursor by n of the `avail` samples (samples_ready) and rewinds the buffer once it is drained.
+static int samples_advance(oaz_engine* e, size_t n, unsigned long long avail) {
+    e->out_read += n;
+    if (e->out_read == avail) {
+        HIP_TRY(hipMemsetAsync(e->out_count, 0, sizeof(unsigned long long), e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        e->out_read = 0;
+    }
+    return 0;
+}
+
 extern "C" int oaz_selfplay_stats_get(oaz_engine* e, oaz_selfplay_stats* o) {
     if (!e || !o) return oaz_set_err(OAZ_ERR_ARG, "selfplay_stats: null");
     OAZ_ON_DEVICE(e->device);
     uint64_t s[GS_COUNT];
     if (int rc = reduce_stats(e, e->G, s)) return rc;
-    unsigned long long cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, e->out_count, sizeof(cnt), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    size_t ready = 0;
+    unsigned long long avail = 0;
+    if (int rc = samples_ready(e, &ready, &avail)) return rc;
     memset(o, 0, sizeof(*o));
     o->moves = s[GS_MOVES];
     o->games_finished = s[GS_FINISHED];
@@ -1289,28 +1244,20 @@ extern "C" int oaz_selfplay_stats_get(oaz_engine* e, oaz_selfplay_stats* o) {
     o->blue_wins = s[GS_BLUE];
     o->passes = s[GS_PASSES];
     o->samples_dropped = s[GS_DROPPED];
-    const unsigned long long avail = cnt < e->out_cap ? cnt : e->out_cap;
-    o->samples_ready = avail > e->out_read ? avail - e->out_read : 0;
+    o->samples_ready = ready;
     fill_search_stats(s, &o->search);
     return 0;
 }
 
 static int samples_copy(oaz_engine* e, void* dst, size_t cap, size_t* n_out, hipMemcpyKind kind) {
     OAZ_ON_DEVICE(e->device);
-    unsigned long long cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, e->out_count, sizeof(cnt), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const unsigned long long avail = (cnt < e->out_cap ? cnt : e->out_cap);
-    const size_t ready = avail > e->out_read ? (size_t)(avail - e->out_read) : 0;
+    size_t ready = 0;
+    unsigned long long avail = 0;
+    if (int rc = samples_ready(e, &ready, &avail)) return rc;
     const size_t n = ready < cap ? ready : cap;
     if (n) HIP_TRY(hipMemcpyAsync(dst, e->out + e->out_read, n * sizeof(oaz_sample), kind, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    e->out_read += n;
-    if (e->out_read == avail && cnt >= e->out_read) {  // buffer drained: rewind
-        HIP_TRY(hipMemsetAsync(e->out_count, 0, sizeof(unsigned long long), e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        e->out_read = 0;
-    }
+    if (int rc = samples_advance(e, n, avail)) return rc;
     if (n_out) *n_out = n;
     return 0;
 }
@@ -1320,11 +1267,8 @@ static int samples_copy(oaz_engine* e, void* dst, size_t cap, size_t* n_out, hip
 int oaz_engine_samples_peek(oaz_engine* e, const oaz_sample** dev, size_t* n, int* device) {
     OAZ_ON_DEVICE(e->device);
     HIP_TRY(hipStreamSynchronize(e->stream2));
-    unsigned long long cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, e->out_count, sizeof(cnt), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const unsigned long long avail = (cnt < e->out_cap ? cnt : e->out_cap);
-    *n = avail > e->out_read ? (size_t)(avail - e->out_read) : 0;
+    unsigned long long avail = 0;
+    if (int rc = samples_ready(e, n, &avail)) return rc;
     *dev = e->out + e->out_read;
     *device = e->device;
     return 0;
@@ -1333,17 +1277,10 @@ int oaz_engine_samples_peek(oaz_engine* e, const oaz_sample** dev, size_t* n, in
 // Drops the first n peeked samples (the caller's copies of them are complete).
 int oaz_engine_samples_consume(oaz_engine* e, size_t n) {
     OAZ_ON_DEVICE(e->device);
-    unsigned long long cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, e->out_count, sizeof(cnt), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const unsigned long long avail = (cnt < e->out_cap ? cnt : e->out_cap);
-    e->out_read += n;
-    if (e->out_read == avail && cnt >= e->out_read) {  // buffer drained: rewind
-        HIP_TRY(hipMemsetAsync(e->out_count, 0, sizeof(unsigned long long), e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        e->out_read = 0;
-    }
-    return 0;
+    size_t ready = 0;
+    unsigned long long avail = 0;
+    if (int rc = samples_ready(e, &ready, &avail)) return rc;
+    return samples_advance(e, n, avail);
 }
 
 extern "C" int oaz_samples_fetch(oaz_engine* e, oaz_sample* out, size_t cap, size_t* n_out) {

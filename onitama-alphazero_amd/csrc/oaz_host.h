@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <stddef.h>
+
 #include "../../include/onitama_az.h"
 
 // Records the thread-local error message returned by oaz_last_error(); returns `code`.
@@ -34,6 +36,109 @@ struct DeviceScope {
 #define OAZ_ON_DEVICE(dev)       \
     DeviceScope dev_scope_(dev); \
     HIP_TRY(dev_scope_.rc)
+
+// "No HIP device visible" and "device d out of range" for the entry points that take a device number.
+// OAZ_ERR_NO_DEVICE for the first; `range_code` for the second (OAZ_ERR_ARG, the trainer OAZ_ERR_NO_DEVICE).
+inline int oaz_check_device(const char* who, int device, int range_code = OAZ_ERR_ARG) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return oaz_set_err(OAZ_ERR_NO_DEVICE, "%s: no HIP device visible", who);
+    if (device < 0 || device >= n) return oaz_set_err(range_code, "%s: device %d out of range (%d visible)", who, device, n);
+    return 0;
+}
+
+// ---- owners of device resources ----------------------------------------------------------------------
+// Movable, not copyable; a default-made one holds nothing and its destructor does nothing. The destructors
+// run on the calling thread's current device, so whoever deletes a holder of owners is on the holder's
+// device (DeviceScope before delete) and has synchronised the streams the resources were used on. Members
+// are destroyed in reverse declaration order: a holder declares its streams first (destroyed last), then
+// its buffers, then its events (destroyed first). Holders of static lifetime are made with `new` and never
+// deleted: a destructor that calls hipFree while the HIP runtime unloads at process exit can hang.
+
+// A device array of `size()` elements of T.
+template <class T>
+class DevBuf {
+    T* p_ = nullptr;
+    size_t n_ = 0;
+
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) {
+        o.p_ = nullptr;
+        o.n_ = 0;
+    }
+    ~DevBuf() { reset(); }
+    // hipFree waits for the whole device: not for the create, play and read-back path of a live owner.
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    // `count` elements, contents undefined (a zero count still allocates 16 bytes: get() is never null).
+    int alloc(size_t count) {
+        reset();
+        void* q = nullptr;
+        HIP_TRY(hipMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
+        p_ = static_cast<T*>(q);
+        n_ = count;
+        return 0;
+    }
+    // Grow-only: at least `count` elements; growing drops the contents. The old buffer is freed, so the
+    // caller first synchronises the stream that may still use it.
+    int reserve(size_t count) { return count <= n_ ? 0 : alloc(count); }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }
+    operator T*() const { return p_; }  // kernel arguments and offsets read as with a raw pointer
+};
+
+// A non-blocking stream. The destructor waits for the stream's work before it destroys the stream, so a
+// stream declared after a buffer (destroyed before it) is done with the buffer when that is freed.
+class Stream {
+    hipStream_t s_ = nullptr;
+
+public:
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+    ~Stream() {
+        (void)sync();
+        if (s_) (void)hipStreamDestroy(s_);
+    }
+    int create() {
+        HIP_TRY(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
+        return 0;
+    }
+    // Waits for the stream's work (nothing to wait for before create()).
+    hipError_t sync() const { return s_ ? hipStreamSynchronize(s_) : hipSuccess; }
+    operator hipStream_t() const { return s_; }
+};
+
+class Event {
+    hipEvent_t ev_ = nullptr;
+
+public:
+    Event() = default;
+    Event(Event&& o) noexcept : ev_(o.ev_) { o.ev_ = nullptr; }
+    ~Event() {
+        if (ev_) (void)hipEventDestroy(ev_);
+    }
+    int create(unsigned flags = hipEventDisableTiming) {
+        HIP_TRY(hipEventCreateWithFlags(&ev_, flags));
+        return 0;
+    }
+    operator hipEvent_t() const { return ev_; }
+};
+
+// 256-byte aligned sections of one device allocation. The same take() calls run twice: on Carver{nullptr}
+// they only add up (`off` is then the allocation to make), on Carver{allocation} they return the sections.
+struct Carver {
+    char* base;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
 
 // Engine internals used by the communicator (oaz_comm.cpp).
 int oaz_engine_samples_peek(oaz_engine* e, const oaz_sample** dev, size_t* n, int* device);

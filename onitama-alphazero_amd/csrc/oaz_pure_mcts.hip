@@ -335,45 +335,41 @@ extern "C" size_t oaz_pure_mcts_tree_capacity(const oaz_pure_mcts_config* c) {
 namespace {
 struct PureWorkspace {
     std::mutex mu;
-    void* p = nullptr;
-    size_t n = 0;
+    DevBuf<char> buf;  // grow-only
     bool busy = false;
 };
 constexpr int kPureMaxDevices = 64;
-PureWorkspace g_pure_ws[kPureMaxDevices];
+// never deleted: no hipFree while the HIP runtime unloads at process exit (oaz_host.h)
+PureWorkspace* const g_pure_ws = new PureWorkspace[kPureMaxDevices];
 
-// (on the calling thread's current device, which is `dev`)
-hipError_t ws_acquire(int dev, size_t bytes, void** out, bool* kept) {
-    PureWorkspace& w = g_pure_ws[dev];
-    {
-        std::lock_guard<std::mutex> lk(w.mu);
-        if (!w.busy) {
-            if (w.n < bytes) {
-                if (w.p) (void)hipFree(w.p);
-                w.p = nullptr;
-                w.n = 0;
-                if (hipError_t e = hipMalloc(&w.p, bytes)) return e;
-                w.n = bytes;
+// A search's hold on its workspace (on the calling thread's current device, which is `dev`): the device's kept
+// buffer, handed back on return, or a buffer of its own, freed on return.
+struct WorkspaceLease {
+    PureWorkspace* kept = nullptr;
+    DevBuf<char> own;
+    char* p = nullptr;
+    int acquire(int dev, size_t bytes) {
+        PureWorkspace& w = g_pure_ws[dev];
+        {
+            std::lock_guard<std::mutex> lk(w.mu);
+            if (!w.busy) {
+                if (int rc = w.buf.reserve(bytes)) return rc;  // (not busy: no search uses the old buffer)
+                w.busy = true;
+                kept = &w;
+                p = w.buf;
+                return 0;
             }
-            w.busy = true;
-            *out = w.p;
-            *kept = true;
-            return hipSuccess;
         }
+        if (int rc = own.alloc(bytes)) return rc;
+        p = own;
+        return 0;
     }
-    *kept = false;
-    return hipMalloc(out, bytes);
-}
-void ws_release(int dev, void* p, bool kept) {
-    if (!p) return;
-    if (!kept) {
-        (void)hipFree(p);
-        return;
+    ~WorkspaceLease() {
+        if (!kept) return;
+        std::lock_guard<std::mutex> lk(kept->mu);
+        kept->busy = false;
     }
-    std::lock_guard<std::mutex> lk(g_pure_ws[dev].mu);
-    g_pure_ws[dev].busy = false;
-}
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+};
 }  // namespace
 
 extern "C" int oaz_pure_mcts_release_workspace(int device) {
@@ -381,12 +377,10 @@ extern "C" int oaz_pure_mcts_release_workspace(int device) {
     PureWorkspace& w = g_pure_ws[device];
     std::lock_guard<std::mutex> lk(w.mu);
     if (w.busy) return oaz_set_err(OAZ_ERR_STATE, "pure_mcts: the workspace of device %d is in use", device);
-    if (w.p) {
+    if (w.buf) {
         DeviceScope dev_scope_(device);
-        (void)hipFree(w.p);
+        w.buf.reset();
     }
-    w.p = nullptr;
-    w.n = 0;
     return 0;
 }
 
@@ -397,11 +391,7 @@ extern "C" int oaz_pure_mcts_search(const oaz_state* roots, int G, const oaz_pur
         return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: null argument");
     if (cfg->max_playouts < 0 || cfg->min_node_visits < 0 || cfg->rollout_cap < 0)
         return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: negative playouts / min_node_visits / rollout_cap");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return oaz_set_err(OAZ_ERR_NO_DEVICE, "pure_mcts: no HIP device");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: device %d of %d", cfg->device, ndev);
+    if (int rc = oaz_check_device("pure_mcts", cfg->device)) return rc;
     for (int g = 0; g < G; ++g)
         if ((roots[g].to_move & ~1) || (roots[g].cards[0] | roots[g].cards[1] | roots[g].cards[2] | roots[g].cards[3] |
                                         roots[g].cards[4]) > 15)
@@ -414,74 +404,59 @@ extern "C" int oaz_pure_mcts_search(const oaz_state* roots, int G, const oaz_pur
     for (size_t n = 0; n < ln.size(); ++n) ln[n] = logf((float)n);  // (parent.visits as f32).ln()
     pm::Params p{cfg->max_playouts, cfg->min_node_visits, cfg->rollout_cap, cfg->exploration_c, cfg->seed,
                  cfg->game_id0, (uint32_t)cap};
+    // the workspace: roots, ln table, values, moves, statistics, trees
     oaz_state* d_roots = nullptr;
     float *d_ln = nullptr, *d_val = nullptr;
-    oaz_pure_node* d_nodes = nullptr;
     oaz_move* d_mv = nullptr;
     uint64_t* d_st = nullptr;
-    void* ws = nullptr;
-    bool ws_kept = false;
-    // the workspace: roots, ln table, values, moves, statistics, trees (256-byte aligned sections)
-    const size_t o_ln = align256(sizeof(oaz_state) * G), o_val = o_ln + align256(sizeof(float) * ln.size());
-    const size_t o_mv = o_val + align256(sizeof(float) * G), o_st = o_mv + align256(sizeof(oaz_move) * G);
-    const size_t o_nodes = o_st + align256(sizeof(uint64_t) * 8 * G);
-    const size_t ws_bytes = o_nodes + sizeof(oaz_pure_node) * cap * G;
-    int rc = 0;
-    auto fail = [&](hipError_t e, const char* what) {
-        rc = oaz_set_err(OAZ_ERR_HIP, "pure_mcts: %s: %s", what, hipGetErrorString(e));
+    oaz_pure_node* d_nodes = nullptr;
+    auto carve = [&](Carver c) {
+        d_roots = c.take<oaz_state>(G);
+        d_ln = c.take<float>(ln.size());
+        d_val = c.take<float>(G);
+        d_mv = c.take<oaz_move>(G);
+        d_st = c.take<uint64_t>((size_t)8 * G);
+        d_nodes = c.take<oaz_pure_node>(cap * G);
+        return c.off;
     };
-    hipError_t e;
+    const size_t ws_bytes = carve(Carver{nullptr});
     // on cfg->device, on a stream of its own: a search on a worker thread neither lands on the thread's
-    // default device nor waits for (or stalls) the engines searching on the same GPU meanwhile
-    hipStream_t sm = nullptr;
-    int prev_dev = -1;  // the calling thread's current device, restored on return
-    if ((e = hipGetDevice(&prev_dev)) != hipSuccess) prev_dev = -1;
-    if ((e = hipSetDevice(cfg->device)) != hipSuccess) fail(e, "set device");
-    else if ((e = hipStreamCreateWithFlags(&sm, hipStreamNonBlocking)) != hipSuccess) fail(e, "stream");
-    else if (cfg->device >= kPureMaxDevices) rc = oaz_set_err(OAZ_ERR_ARG, "pure_mcts: device %d unsupported", cfg->device);
-    else if ((e = ws_acquire(cfg->device, ws_bytes, &ws, &ws_kept)) != hipSuccess) fail(e, "alloc");
-    if (!rc) {
-        char* b = static_cast<char*>(ws);
-        d_roots = reinterpret_cast<oaz_state*>(b);
-        d_ln = reinterpret_cast<float*>(b + o_ln);
-        d_val = reinterpret_cast<float*>(b + o_val);
-        d_mv = reinterpret_cast<oaz_move*>(b + o_mv);
-        d_st = reinterpret_cast<uint64_t*>(b + o_st);
-        d_nodes = reinterpret_cast<oaz_pure_node*>(b + o_nodes);
-    }
-    if (!rc) {
-        (void)hipMemcpyAsync(d_roots, roots, sizeof(oaz_state) * G, hipMemcpyHostToDevice, sm);
-        (void)hipMemcpyAsync(d_ln, ln.data(), sizeof(float) * ln.size(), hipMemcpyHostToDevice, sm);
-        hipLaunchKernelGGL(pm::k_pure_mcts, dim3((G + 63) / 64), dim3(64), 0, sm, d_roots, G, p, d_ln, d_nodes, d_mv,
-                           d_val, d_st);
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(sm)) != hipSuccess) fail(e, "kernel");
-    }
-    if (!rc) {
-        std::vector<uint64_t> st((size_t)G * 8);
-        (void)hipMemcpyAsync(out_move, d_mv, sizeof(oaz_move) * G, hipMemcpyDeviceToHost, sm);
-        (void)hipMemcpyAsync(out_value, d_val, sizeof(float) * G, hipMemcpyDeviceToHost, sm);
-        (void)hipMemcpyAsync(st.data(), d_st, sizeof(uint64_t) * st.size(), hipMemcpyDeviceToHost, sm);
-        if ((e = hipStreamSynchronize(sm)) != hipSuccess) fail(e, "copy");
-        if (stats && !rc)
-            for (int g = 0; g < G; ++g) {
-                stats->playouts += st[g * 8 + 0];
-                stats->expansions += st[g * 8 + 1];
-                stats->rollout_plies += st[g * 8 + 2];
-                stats->rollout_passes += st[g * 8 + 3];
-                stats->rollouts_capped += st[g * 8 + 4];
-                if (st[g * 8 + 5] > stats->max_nodes) stats->max_nodes = st[g * 8 + 5];
-                stats->tree_full += st[g * 8 + 6];
-            }
-        if (tree_out && tree_cap && !rc) {
-            for (int g = 0; g < G; ++g)
-                (void)hipMemcpyAsync(tree_out + (size_t)g * tree_cap, d_nodes + (size_t)g * cap,
-                                     sizeof(oaz_pure_node) * (tree_cap < cap ? tree_cap : cap), hipMemcpyDeviceToHost, sm);
-            if ((e = hipStreamSynchronize(sm)) != hipSuccess) fail(e, "tree copy");
+    // default device nor waits for (or stalls) the engines searching on the same GPU meanwhile. The stream is
+    // declared after the workspace: on every return it is waited for before the workspace goes back or is freed
+    // (and before `st` goes).
+    OAZ_ON_DEVICE(cfg->device);
+    std::vector<uint64_t> st((size_t)G * 8);
+    WorkspaceLease ws;
+    Stream sm;
+    if (int rc = sm.create()) return rc;
+    if (cfg->device >= kPureMaxDevices) return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: device %d unsupported", cfg->device);
+    if (int rc = ws.acquire(cfg->device, ws_bytes)) return rc;
+    carve(Carver{ws.p});
+    HIP_TRY(hipMemcpyAsync(d_roots, roots, sizeof(oaz_state) * G, hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_ln, ln.data(), sizeof(float) * ln.size(), hipMemcpyHostToDevice, sm));
+    hipLaunchKernelGGL(pm::k_pure_mcts, dim3((G + 63) / 64), dim3(64), 0, sm, d_roots, G, p, d_ln, d_nodes, d_mv, d_val,
+                       d_st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(sm));
+    HIP_TRY(hipMemcpyAsync(out_move, d_mv, sizeof(oaz_move) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(out_value, d_val, sizeof(float) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(st.data(), d_st, sizeof(uint64_t) * st.size(), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipStreamSynchronize(sm));
+    if (stats)
+        for (int g = 0; g < G; ++g) {
+            stats->playouts += st[g * 8 + 0];
+            stats->expansions += st[g * 8 + 1];
+            stats->rollout_plies += st[g * 8 + 2];
+            stats->rollout_passes += st[g * 8 + 3];
+            stats->rollouts_capped += st[g * 8 + 4];
+            if (st[g * 8 + 5] > stats->max_nodes) stats->max_nodes = st[g * 8 + 5];
+            stats->tree_full += st[g * 8 + 6];
         }
+    if (tree_out && tree_cap) {
+        for (int g = 0; g < G; ++g)
+            HIP_TRY(hipMemcpyAsync(tree_out + (size_t)g * tree_cap, d_nodes + (size_t)g * cap,
+                                   sizeof(oaz_pure_node) * (tree_cap < cap ? tree_cap : cap), hipMemcpyDeviceToHost, sm));
+        HIP_TRY(hipStreamSynchronize(sm));
     }
-    if (sm) (void)hipStreamSynchronize(sm);
-    if (ws) ws_release(cfg->device, ws, ws_kept);
-    if (sm) (void)hipStreamDestroy(sm);
-    if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
-    return rc;
+    return 0;
 }

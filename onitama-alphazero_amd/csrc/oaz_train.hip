@@ -1006,66 +1006,54 @@ static Layout make_layout(int blocks) {  // weights.py canonical_layout / VarSto
     return L;
 }
 
+// The device resources are owning members (oaz_host.h), destroyed in reverse declaration order after
+// oaz_trainer_destroy waited for the device: events (declared last) first, then the buffers, the streams
+// (declared first) last. Keep that order when adding a member.
 struct oaz_trainer {
     oaz_train_config cfg{};
     int device = 0;
-    hipStream_t own = nullptr, st = nullptr;
-    hipStream_t st2 = nullptr;  // weight-gradient stream: wgrad(l) overlaps dgrad(l) on st
-    hipEvent_t ev_dz[2] = {}, ev_w[2] = {}, ev_h[2] = {}, ev_done = nullptr;
+    Stream own;                // the trainer's stream
+    hipStream_t st = nullptr;  // the stream its work runs on: own, or the caller's (oaz_trainer_set_stream)
+    Stream st2;                // weight-gradient stream: wgrad(l) overlaps dgrad(l) on st
     Layout L{};
     int nconv = 0, maxB = 0;
     int cfin = -1;     // forward BN finalisation in k_bn_act_cfin (-1: one float4 per thread; A/B build: 0 = the
                        // separate k_bn_fwd_fin + k_bn_act launches, n > 0 = n workgroups)
     int conv_rg = 2;  // 16-row groups per conv workgroup (OAZ_CONV_RG=1|2|4 overrides; tuning knob)
     size_t nparam = 0;
-    std::vector<void*> allocs;
-    float *P = nullptr, *G = nullptr, *MOM = nullptr;
-    uint8_t* mask = nullptr;
-    float4 *wf[kMaxConv] = {}, *wd[kMaxConv] = {};
-    float *X0 = nullptr, *Z[kMaxConv] = {}, *A[kMaxConv] = {}, *M[kMaxConv] = {}, *DZ[2] = {};
-    float *mean[kMaxConv] = {}, *invstd[kMaxConv] = {}, *bcoef = nullptr;  // bcoef: c1, mm, mx [3][64]
-    float *part = nullptr, *bpart[2] = {}, *wpart = nullptr;
-    float *hz = nullptr, *g3 = nullptr, *hstat = nullptr;  // hstat: mean[3] invstd[3] c1[3] mm[3] mx[3]
-    float *hpart = nullptr, *hwpart = nullptr, *hlpart = nullptr, *hcpart = nullptr;
-    float *pi = nullptr, *z = nullptr;
-    const oaz_sample* samples = nullptr;
-    oaz_sample* owned_samples = nullptr;
-    size_t n_samples = 0, owned_cap = 0;
-    int32_t* idx = nullptr;
+    DevBuf<float> P, G, MOM;
+    DevBuf<uint8_t> mask;
+    DevBuf<float4> wf[kMaxConv], wd[kMaxConv];
+    DevBuf<float> X0, Z[kMaxConv], A[kMaxConv], M[kMaxConv], DZ[2];
+    DevBuf<float> mean[kMaxConv], invstd[kMaxConv], bcoef;  // bcoef: c1, mm, mx [3][64]
+    DevBuf<float> part, bpart[2], wpart;
+    DevBuf<float> hz, g3, hstat;  // hstat: mean[3] invstd[3] c1[3] mm[3] mx[3]
+    DevBuf<float> hpart, hwpart, hlpart, hcpart;
+    DevBuf<float> pi, z;
+    const oaz_sample* samples = nullptr;  // owned_samples, or the caller's (oaz_trainer_bind_device_samples)
+    DevBuf<oaz_sample> owned_samples;     // grow-only
+    size_t n_samples = 0;
+    DevBuf<int32_t> idx;  // grow-only
     int n_batches = 0, batch = 0;
-    size_t idx_cap = 0;
-    double* loss_acc = nullptr;
-    int32_t* cur = nullptr;  // current batch number (device)
+    DevBuf<double> loss_acc;
+    DevBuf<int32_t> cur;  // current batch number (device)
+    Event ev_dz[2], ev_w[2], ev_h[2], ev_done;  // (after the buffers: destroyed before them)
     // one captured SGD step (gather -> ... -> SGD -> batch+1), replayed by oaz_trainer_train
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     const void* graph_key[3] = {nullptr, nullptr, nullptr};
     int graph_batch = 0;
 
+    // `count` elements and a 16-byte pad, zero-filled on the trainer's stream: ordered before its work (create syncs)
     template <class T>
-    int alloc(T*& p, size_t count) {
-        void* q = nullptr;
-        HIP_TRY(hipMalloc(&q, count * sizeof(T) + 16));
-        HIP_TRY(hipMemsetAsync(q, 0, count * sizeof(T) + 16, own));  // ordered before the trainer's work (create syncs)
-        allocs.push_back(q);
-        p = (T*)q;
+    int alloc(DevBuf<T>& b, size_t count) {
+        if (int rc = b.alloc(count + 16 / sizeof(T))) return rc;
+        HIP_TRY(hipMemsetAsync(b, 0, b.size() * sizeof(T), own));
         return 0;
     }
-    ~oaz_trainer() {
-        if (owned_samples) (void)hipFree(owned_samples);
-        if (idx) (void)hipFree(idx);
-        for (void* q : allocs) (void)hipFree(q);
-        for (int k = 0; k < 2; ++k) {
-            if (ev_dz[k]) (void)hipEventDestroy(ev_dz[k]);
-            if (ev_w[k]) (void)hipEventDestroy(ev_w[k]);
-        }
-        if (ev_done) (void)hipEventDestroy(ev_done);
-        for (hipEvent_t ev : ev_h)
-            if (ev) (void)hipEventDestroy(ev);
+    ~oaz_trainer() {  // what the members do not own
         if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
         if (graph) (void)hipGraphDestroy(graph);
-        if (st2) (void)hipStreamDestroy(st2);
-        if (own) (void)hipStreamDestroy(own);
     }
 };
 
@@ -1082,17 +1070,52 @@ extern "C" void oaz_train_config_default(oaz_train_config* c) {
     c->value_loss_broadcast = 1;
 }
 
+// The device side of oaz_trainer_create (on the trainer's device). On an error the trainer is partly built;
+// its destructor takes it as it is (a member not made yet holds nothing).
+static int trainer_init(oaz_trainer* t) {
+    const size_t R = (size_t)t->maxB * 25;
+    if (t->st2.create() || t->ev_done.create() || t->own.create()) return OAZ_ERR_HIP;
+    for (int k = 0; k < 2; ++k)
+        if (t->ev_dz[k].create() || t->ev_w[k].create() || t->ev_h[k].create()) return OAZ_ERR_HIP;
+    t->st = t->own;
+    if (t->alloc(t->P, t->nparam) || t->alloc(t->G, t->nparam) || t->alloc(t->MOM, t->nparam) ||
+        t->alloc(t->mask, t->nparam))
+        return OAZ_ERR_HIP;  // (here and below: HIP_TRY recorded the call and the HIP error)
+    for (int l = 0; l < t->nconv; ++l) {
+        const int chunks = l == 0 ? 2 : 4;
+        if (t->alloc(t->wf[l], (size_t)9 * chunks * 256)) return OAZ_ERR_HIP;
+        if (l > 0 && t->alloc(t->wd[l], (size_t)9 * chunks * 256)) return OAZ_ERR_HIP;
+        if (t->alloc(t->Z[l], R * kC) || t->alloc(t->A[l], R * kC) || t->alloc(t->M[l], R * kC) ||
+            t->alloc(t->mean[l], 64) || t->alloc(t->invstd[l], 64))
+            return OAZ_ERR_HIP;
+    }
+    const size_t nwg_conv = R / 16;
+    if (t->alloc(t->X0, R * kInPad) || t->alloc(t->DZ[0], R * kC) || t->alloc(t->DZ[1], R * kC) || t->alloc(t->bcoef, 3 * 64) ||
+        t->alloc(t->part, nwg_conv * 128) || t->alloc(t->bpart[0], (R + 15) / 16 * 64) || t->alloc(t->bpart[1], (R + 15) / 16 * 64) ||
+        t->alloc(t->wpart, (size_t)9 * 25 * kWSplit * 64 * 64) || t->alloc(t->hz, R * 4) || t->alloc(t->g3, R * 4) ||
+        t->alloc(t->hstat, 16) || t->alloc(t->hpart, ((R + 255) / 256 + (size_t)t->maxB / kHS + 1) * 8) ||
+        t->alloc(t->hwpart, ((size_t)t->maxB / kHS + 1) * kHeadW) ||
+        t->alloc(t->hlpart, ((size_t)t->maxB / kHS + 1) * 2) ||
+        t->alloc(t->hcpart, ((R + 63) / 64) * (size_t)kHConvW) || t->alloc(t->pi, (size_t)t->maxB * 50) ||
+        t->alloc(t->z, (size_t)t->maxB) || t->alloc(t->loss_acc, 4) || t->alloc(t->cur, 1))
+        return OAZ_ERR_HIP;
+    std::vector<uint8_t> mask(t->nparam, 1);
+    for (int l = 0; l < t->nconv; ++l)
+        for (int c = 0; c < 64; ++c) mask[t->L.brm[l] + c] = mask[t->L.brv[l] + c] = 0;
+    mask[t->L.h.vrm] = mask[t->L.h.vrv] = 0;
+    mask[t->L.h.prm] = mask[t->L.h.prm + 1] = mask[t->L.h.prv] = mask[t->L.h.prv + 1] = 0;
+    HIP_TRY(hipMemcpyAsync(t->mask, mask.data(), t->nparam, hipMemcpyHostToDevice, t->own));
+    HIP_TRY(hipStreamSynchronize(t->own));  // the zero fills and the mask landed before any step
+    return 0;
+}
+
 extern "C" oaz_trainer* oaz_trainer_create(const oaz_train_config* cfg, int device) {
     if (!cfg || cfg->blocks < 0 || cfg->blocks > 16 || cfg->max_batch < 16 || cfg->max_batch % 16 ||
         cfg->max_batch > (1 << 16)) {
         oaz_set_err(OAZ_ERR_ARG, "trainer: blocks in [0,16], max_batch a multiple of 16 in [16, 65536]");
         return nullptr;
     }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) {
-        oaz_set_err(OAZ_ERR_NO_DEVICE, "trainer: no HIP device %d", device);
-        return nullptr;
-    }
+    if (oaz_check_device("trainer", device, OAZ_ERR_NO_DEVICE)) return nullptr;
     DeviceScope dev_scope_(device);  // the caller's current device is restored on return
     if (dev_scope_.rc != hipSuccess) {
         oaz_set_err(OAZ_ERR_NO_DEVICE, "trainer: hipSetDevice(%d) failed", device);
@@ -1112,49 +1135,9 @@ extern "C" oaz_trainer* oaz_trainer_create(const oaz_train_config* cfg, int devi
     if (const char* e = getenv("OAZ_TRAIN_CFIN")) t->cfin = atoi(e) > 0 ? atoi(e) : 0;
 #endif
     t->nparam = t->L.total;
-    const size_t R = (size_t)t->maxB * 25;
-    auto fail = [&]() -> oaz_trainer* { delete t; return nullptr; };
-    bool ev_ok = hipStreamCreateWithFlags(&t->st2, hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&t->ev_done, hipEventDisableTiming) == hipSuccess;
-    for (int k = 0; k < 2 && ev_ok; ++k)
-        ev_ok = hipEventCreateWithFlags(&t->ev_dz[k], hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&t->ev_w[k], hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&t->ev_h[k], hipEventDisableTiming) == hipSuccess;
-    if (!ev_ok || hipStreamCreateWithFlags(&t->own, hipStreamNonBlocking) != hipSuccess) {
-        oaz_set_err(OAZ_ERR_HIP, "trainer: stream");
-        return fail();
-    }
-    t->st = t->own;
-    if (t->alloc(t->P, t->nparam) || t->alloc(t->G, t->nparam) || t->alloc(t->MOM, t->nparam) ||
-        t->alloc(t->mask, t->nparam))
-        return fail();
-    for (int l = 0; l < t->nconv; ++l) {
-        const int chunks = l == 0 ? 2 : 4;
-        if (t->alloc(t->wf[l], (size_t)9 * chunks * 256)) return fail();
-        if (l > 0 && t->alloc(t->wd[l], (size_t)9 * chunks * 256)) return fail();
-        if (t->alloc(t->Z[l], R * kC) || t->alloc(t->A[l], R * kC) || t->alloc(t->M[l], R * kC) ||
-            t->alloc(t->mean[l], 64) || t->alloc(t->invstd[l], 64))
-            return fail();
-    }
-    const size_t nwg_conv = R / 16;
-    if (t->alloc(t->X0, R * kInPad) || t->alloc(t->DZ[0], R * kC) || t->alloc(t->DZ[1], R * kC) || t->alloc(t->bcoef, 3 * 64) ||
-        t->alloc(t->part, nwg_conv * 128) || t->alloc(t->bpart[0], (R + 15) / 16 * 64) || t->alloc(t->bpart[1], (R + 15) / 16 * 64) ||
-        t->alloc(t->wpart, (size_t)9 * 25 * kWSplit * 64 * 64) || t->alloc(t->hz, R * 4) || t->alloc(t->g3, R * 4) ||
-        t->alloc(t->hstat, 16) || t->alloc(t->hpart, ((R + 255) / 256 + (size_t)t->maxB / kHS + 1) * 8) ||
-        t->alloc(t->hwpart, ((size_t)t->maxB / kHS + 1) * kHeadW) ||
-        t->alloc(t->hlpart, ((size_t)t->maxB / kHS + 1) * 2) ||
-        t->alloc(t->hcpart, ((R + 63) / 64) * (size_t)kHConvW) || t->alloc(t->pi, (size_t)t->maxB * 50) ||
-        t->alloc(t->z, (size_t)t->maxB) || t->alloc(t->loss_acc, 4) || t->alloc(t->cur, 1))
-        return fail();
-    std::vector<uint8_t> mask(t->nparam, 1);
-    for (int l = 0; l < t->nconv; ++l)
-        for (int c = 0; c < 64; ++c) mask[t->L.brm[l] + c] = mask[t->L.brv[l] + c] = 0;
-    mask[t->L.h.vrm] = mask[t->L.h.vrv] = 0;
-    mask[t->L.h.prm] = mask[t->L.h.prm + 1] = mask[t->L.h.prv] = mask[t->L.h.prv + 1] = 0;
-    if (hipMemcpyAsync(t->mask, mask.data(), t->nparam, hipMemcpyHostToDevice, t->own) != hipSuccess ||
-        hipStreamSynchronize(t->own) != hipSuccess) {  // the zero fills and the mask landed before any step
-        oaz_set_err(OAZ_ERR_HIP, "trainer: mask upload");
-        return fail();
+    if (trainer_init(t)) {  // the one failure exit: the partly built trainer goes, the error text stays
+        oaz_trainer_destroy(t);
+        return nullptr;
     }
     return t;
 }
@@ -1211,13 +1194,9 @@ extern "C" int oaz_trainer_save_ot(oaz_trainer* t, const char* path) {
 extern "C" int oaz_trainer_load_samples(oaz_trainer* t, const oaz_sample* s, size_t n) {
     if (!t || (!s && n)) return oaz_set_err(OAZ_ERR_ARG, "trainer: null samples");
     OAZ_ON_DEVICE(t->device);
-    if (n > t->owned_cap) {
-        HIP_TRY(hipStreamSynchronize(t->st));
-        if (t->owned_samples) HIP_TRY(hipFree(t->owned_samples));
-        t->owned_samples = nullptr;
-        t->owned_cap = 0;
-        HIP_TRY(hipMalloc(&t->owned_samples, n * sizeof(oaz_sample)));
-        t->owned_cap = n;
+    if (n > t->owned_samples.size()) {
+        HIP_TRY(hipStreamSynchronize(t->st));  // the old buffer is freed: after the work that reads it
+        if (int rc = t->owned_samples.reserve(n)) return rc;
     }
     if (n) HIP_TRY(hipMemcpyAsync(t->owned_samples, s, n * sizeof(oaz_sample), hipMemcpyHostToDevice, t->st));
     HIP_TRY(hipStreamSynchronize(t->st));
@@ -1241,13 +1220,9 @@ extern "C" int oaz_trainer_set_batches(oaz_trainer* t, const int32_t* idx, int n
         if (idx[i] < 0 || (size_t)idx[i] >= t->n_samples)
             return oaz_set_err(OAZ_ERR_ARG, "trainer: index %d out of range (%zu samples)", idx[i], t->n_samples);
     OAZ_ON_DEVICE(t->device);
-    if (n > t->idx_cap) {
-        HIP_TRY(hipStreamSynchronize(t->st));
-        if (t->idx) HIP_TRY(hipFree(t->idx));
-        t->idx = nullptr;
-        t->idx_cap = 0;
-        HIP_TRY(hipMalloc(&t->idx, n * sizeof(int32_t)));
-        t->idx_cap = n;
+    if (n > t->idx.size()) {
+        HIP_TRY(hipStreamSynchronize(t->st));  // the old buffer is freed: after the work that reads it
+        if (int rc = t->idx.reserve(n)) return rc;
     }
     if (n) HIP_TRY(hipMemcpyAsync(t->idx, idx, n * sizeof(int32_t), hipMemcpyHostToDevice, t->st));
     HIP_TRY(hipStreamSynchronize(t->st));
@@ -1431,8 +1406,8 @@ static int apply(oaz_trainer* t, float scale) {
     for (int l = 0; l < t->nconv; ++l) {
         tab.off[l] = (int)t->L.cw[l];
         tab.cin[l] = l == 0 ? kIn : kC;
-        tab.wf[l] = reinterpret_cast<float*>(t->wf[l]);
-        tab.wd[l] = reinterpret_cast<float*>(t->wd[l]);
+        tab.wf[l] = reinterpret_cast<float*>(t->wf[l].get());
+        tab.wd[l] = reinterpret_cast<float*>(t->wd[l].get());
     }
     hipLaunchKernelGGL(k_sgd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, t->st, t->P, t->G, t->MOM, t->mask, n,
                        (float)t->cfg.learning_rate, (float)t->cfg.momentum, (float)t->cfg.weight_decay, scale, tab);
