@@ -563,6 +563,97 @@ int oaz_alphabeta_evaluate(const oaz_state* s, const uint8_t* move_result, int n
 int oaz_alphabeta_search(const oaz_state* roots, int G, const oaz_alphabeta_config* cfg,
                          oaz_move* out_move, int32_t* out_score, oaz_alphabeta_stats* stats);
 
+/* ---- arena: a fight played on the device (Evaluator, alphazero-training/src/evaluator.rs) -----------
+ * fight (evaluator.rs:355-399) with all game_amnt games advanced together and their states resident on the
+ * GPU: every ply the active games are routed to the side that moves in them (ascending game index), each
+ * side answers its games in one batched search, and the moves are applied on the device. Game k is dealt
+ * oaz_deal_deck(seed, k) (or the fixed deck) and starts from oaz_initial_state, the neutral card's colour
+ * moving first (game_state.rs:37-45), or from cfg->start[k]; the agent plays Red in even
+ * games and Blue in odd ones (`agents.reverse()`, evaluator.rs:397). A pass (from == 25; the searches'
+ * answer for a root without a legal move) rotates cards[slot] with the neutral card and flips the side to
+ * move (state.rs:139-142). A game ends on a win, or after the ply on which the budget (max_plies, one less
+ * after every ply) was already negative (evaluator.rs:376-389: 152 plies at max_plies 150, 2 at 0, 1 at -1).
+ * Elo and the counters are folded on the host in game order after the last ply (FightStatistics::update,
+ * evaluator.rs:52-99), so the statistics equal the reference's one-game-after-the-other loop. */
+enum {                       /* the Agent implementations a side can be */
+    OAZ_AGENT_ALPHAZERO = 0, /* AlphaZeroMcts, alphazero_mcts/mod.rs:122-161 (evaluator.rs:198-204) */
+    OAZ_AGENT_RANDOM = 1,    /* Random, onitama-game/src/ai/random.rs:11-43 */
+    OAZ_AGENT_PURE_MCTS = 2, /* Mcts, onitama-game/src/ai/mcts/mod.rs:37-52 (evaluator.rs:340-345) */
+    OAZ_AGENT_ALPHABETA = 3  /* AlphaBeta, onitama-game/src/ai/alpha_beta/mod.rs:136-170 (evaluator.rs:303-306) */
+};
+
+typedef struct oaz_arena_agent {
+    int32_t kind;
+    int32_t reserved;
+    oaz_engine* engine;             /* ALPHAZERO: a created engine on cfg->device (its weights: oaz_load_weights; or OAZ_EVAL_HASH),
+                                       searched with its current sims / c_puct / noise / search_time settings. Both
+                                       sides may name the same engine: their searches of a ply then run one after
+                                       the other */
+    uint64_t seed;                  /* RANDOM: the Philox key of oaz_random_agent_move */
+    oaz_pure_mcts_config mcts;      /* PURE_MCTS: seed inside; device and game_id0 are set by the arena: game_id0 =
+                                       c << 20 for this side's c-th search of the fight, root g of a search being
+                                       the side's g-th game in ascending game index */
+    oaz_alphabeta_config alphabeta; /* ALPHABETA (device is set by the arena) */
+} oaz_arena_agent; /* 88 bytes */
+
+typedef struct oaz_arena_config { /* EvaluatorConfig, evaluator.rs:120-137 (winrate_percent is the caller's) */
+    int32_t game_amnt;            /* 20 */
+    int32_t max_plies;            /* 150 */
+    int32_t fixed_deck;           /* 1: every game uses deck[]; 0: game k is dealt oaz_deal_deck(seed, k) */
+    int32_t device;               /* the HIP device the fight runs on */
+    uint8_t deck[5];
+    uint8_t pad[3];
+    uint64_t seed;
+    const oaz_state* start;       /* optional (NULL: deal): game k starts from start[k], its to_move moving first (an
+                                     opening book, a test position); deck, fixed_deck and seed are then unused */
+} oaz_arena_config; /* 40 bytes */
+
+typedef struct oaz_fight_stats { /* FightStatistics, evaluator.rs:37-110 (the agent is "a") */
+    double rating_a, rating_b;
+    double winrate;              /* wins / games (update_winrate, evaluator.rs:101-109); 0 before the first game */
+    double color_winrate[2];     /* as Red, as Blue; NaN for a colour without games once a game was folded (Rust's 0 / 0) */
+    uint32_t wins, loses, draws;
+    uint32_t color_wins[2], color_loses[2], color_draws[2];
+    uint32_t reserved;
+    uint64_t plies_total;        /* moves made over all games (oaz_arena_fight only) */
+    uint64_t passes;             /* of them passes (oaz_arena_fight only) */
+} oaz_fight_stats; /* 96 bytes */
+
+void oaz_arena_config_default(oaz_arena_config* cfg);   /* EvaluatorConfig::default, evaluator.rs:129-136 */
+/* EloRating::elo_change (elo_rating.rs:56-71; K = 32, C = 1 / 400). Host only. */
+void oaz_elo_change(double ra, double rb, int a_won, double* ra_out, double* rb_out);
+/* FightStatistics::update (evaluator.rs:52-99) folded over n MoveResult codes in game order, game k played by the
+ * agent as Red when k is even; anything but a win is a draw. history (optional): n x 4 doubles (before_a,
+ * after_a, before_b, after_b), the RatingChange records (evaluator.rs:29-35). Host only. */
+int oaz_fight_stats_fold(const uint8_t* results, int n, double rating_a, double rating_b, oaz_fight_stats* out,
+                         double* history);
+/* Random::generate_move (ai/random.rs:11-43) for global game `game` at ply `ply` of the mover s->to_move: the two
+ * draws are words 0 and 1 of Philox4x32-10(seed; game lo, game hi, 0x52414E44, ply): card_idx = (w0 * 2) >> 32
+ * among the mover's two cards, then move (w1 * n) >> 32 of that card's n legal moves in generate_legal_moves
+ * order (state.rs:301-378; from, to ascending). out->slot = card_idx (0 / 1 for Blue too, random.rs:39); with
+ * n == 0 the move is {from 0, to 5, pawn} (random.rs:27-33). Host only; the arena's kernel runs the same body. */
+int oaz_random_agent_move(uint64_t seed, uint64_t game, uint32_t ply, const oaz_state* s, oaz_move* out);
+/* The largest batch each side answers in a fight of cfg (out[0] the agent's, out[1] the opponent's): the games
+ * move in lock step, so a side moves in the games whose first mover (the neutral card's colour,
+ * game_state.rs:37-45) it is on even plies and in the others on odd ones: ceil(game_amnt / 2) for a fixed
+ * deck, up to game_amnt for random deals. An ALPHAZERO side's engine needs at least that many `games`. Host only. */
+int oaz_arena_capacity(const oaz_arena_config* cfg, int32_t out[2]);
+/* fight (evaluator.rs:355-399). results / plies (optional, game_amnt each): every game's last MoveResult (a
+ * draw is OAZ_CAPTURE or OAZ_IN_PROGRESS) and the moves it made; history as oaz_fight_stats_fold's. Runs on
+ * cfg->device on streams of its own and the engines'; the sides' searches of a ply overlap unless they share an
+ * engine. PURE_MCTS and ALPHABETA sides go through oaz_pure_mcts_search / oaz_alphabeta_search with their roots
+ * and moves staged in pinned host memory (24 B down, 4 B up per root and ply). Calls on disjoint engines may
+ * run on several host threads at once. The calling thread's current HIP device is restored before the call
+ * returns. Checked before any device is touched: null cfg / agent / opponent / stats or game_amnt < 0, an
+ * unknown kind, ALPHAZERO without an engine or with an engine on another device, a
+ * fixed deck with a card >= 16 or a repeated card, a start position that is not a valid state,
+ * alphabeta.max_depth outside 2..6 (OAZ_ERR_ARG), and an
+ * engine with fewer `games` than oaz_arena_capacity asks for (OAZ_ERR_CAPACITY). game_amnt == 0 returns
+ * empty statistics without touching a device. */
+int oaz_arena_fight(const oaz_arena_config* cfg, const oaz_arena_agent* agent, const oaz_arena_agent* opponent,
+                    double agent_rating, double opponent_rating, oaz_fight_stats* stats, uint8_t* results,
+                    int32_t* plies, double* history);
+
 #ifdef __cplusplus
 }
 #endif

@@ -444,6 +444,50 @@ OAZ_HD int32_t alphabeta_evaluate(const oaz_state& s, int color, bool won) {
     return sign * (pieces + temple + close + squares);
 }
 
+// ---- Random agent: onitama-game/src/ai/random.rs:11-43 ------------------------------------------------
+// One body for the host entry (oaz_random_agent_move) and the arena kernel (oaz_arena.hip). The reference
+// draws from thread_rng; here the two draws of game `game` at ply `ply` are words 0 and 1 of
+// Philox(seed; game lo, game hi, 0x52414E44 "RAND", ply): card_idx = (w0 * 2) >> 32 of the mover's two cards,
+// then move number (w1 * n) >> 32 of that card's n legal moves in generate_legal_moves order (from, to
+// ascending: the order k_movegen emits for the slot). The quirks are kept (Q15): used_card_idx is 0 / 1 for
+// Blue too, and without a legal move of the drawn card the move is a5 -> a4 with a pawn.
+OAZ_HD void random_agent_move(const AttackTable& att, uint64_t seed, uint64_t game, uint32_t ply, const oaz_state& s,
+                              oaz_move& out) {
+    const u32x4 r = philox(seed, (uint32_t)game, (uint32_t)(game >> 32), 0x52414E44u, ply);
+    const int card_idx = (int)(((uint64_t)r.x * 2u) >> 32);
+    const bool blue = (s.to_move & 1) != 0;
+    const uint32_t pawns = blue ? s.pawns[1] : s.pawns[0], king = blue ? s.kings[1] : s.kings[0];
+    const uint32_t own = (pawns | king) & 0xFFFFFF80u;  // squares 0..24 only: they index the table
+    const uint32_t* row = att.m[blue ? 1 : 0][state_card(s, (blue ? 2 : 0) + card_idx) & 15];
+    uint32_t n = 0;
+    for (uint32_t o = own; o;) {
+        const int from = __builtin_clz(o);
+        o &= ~sq_bit(from);
+        n += (uint32_t)__builtin_popcount(row[from] & ~own);
+    }
+    out.from = 0;
+    out.to = 5;
+    out.piece = OAZ_PAWN;
+    out.slot = (uint8_t)card_idx;
+    if (n == 0) return;
+    uint32_t k = (uint32_t)(((uint64_t)r.y * (uint64_t)n) >> 32);
+    for (uint32_t o = own; o;) {
+        const int from = __builtin_clz(o);
+        o &= ~sq_bit(from);
+        uint32_t m = row[from] & ~own;
+        const uint32_t c = (uint32_t)__builtin_popcount(m);
+        if (k >= c) {
+            k -= c;
+            continue;
+        }
+        for (; k; --k) m &= ~sq_bit(__builtin_clz(m));
+        out.from = (uint8_t)from;
+        out.to = (uint8_t)__builtin_clz(m);
+        out.piece = (uint8_t)((pawns & sq_bit(from)) ? OAZ_PAWN : OAZ_KING);
+        return;
+    }
+}
+
 // f64::total_cmp key (argmax ties and signed zeros as Rust orders them)
 OAZ_HD int64_t total_key(double x) {
     int64_t i = (int64_t)__builtin_bit_cast(uint64_t, x);

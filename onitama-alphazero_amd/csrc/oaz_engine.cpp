@@ -1123,6 +1123,38 @@ static void fill_search_stats(const uint64_t* s, oaz_search_stats* o) {
     o->nn_evals = s[GS_EVALS];
 }
 
+// The search of G roots, enqueued on the engine stream (on the engine's device): `roots` (host) are uploaded
+// to s_roots first, or with roots == null the G positions already in s_roots are searched (the arena's
+// device-resident fight, oaz_arena.hip). The moves are left in s_move and pi in s_pi. Without a search_time
+// budget nothing here waits for the device.
+static int search_core(oaz_engine* e, const oaz_state* roots, int G) {
+    if (int rc = begin_budget(e)) return rc;
+    const TreeView t = tree_view(e, (uint32_t)G);
+    if (roots) HIP_TRY(hipMemcpyAsync(e->s_roots, roots, (size_t)G * sizeof(oaz_state), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(e->stats, 0, (size_t)G * GS_COUNT * sizeof(uint64_t), e->stream));
+    // every root's "ply" (the root-noise key) is the number of this engine's earlier searches
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)e->s_ply.get(), (int)e->search_calls, (size_t)G, e->stream));
+    e->search_calls++;
+    HIP_TRY(launch_tree_reset(t, e->stream));
+    if (int rc = run_sims(e, t, e->s_roots, nullptr, nullptr, e->s_ply)) return rc;
+    return timed(e, 3, (uint32_t)G, [&] { return launch_search_finalize(t, e->s_roots, e->s_move, e->s_pi, e->stream); });
+}
+
+// Engine internals used by the arena (oaz_arena.hip, declared in oaz_host.h).
+int oaz_engine_arena_view(oaz_engine* e, oaz_arena_engine_view* out) {
+    if (!e || !out) return oaz_set_err(OAZ_ERR_ARG, "arena: null engine");
+    out->device = e->device;
+    out->games = e->G;
+    out->roots = e->s_roots;
+    out->moves = e->s_move;
+    out->stream = e->stream;
+    return 0;
+}
+int oaz_engine_search_resident(oaz_engine* e, int G) {
+    if (!e || G < 0 || (uint32_t)G > e->G) return oaz_set_err(OAZ_ERR_CAPACITY, "arena: %d roots > the engine's games", G);
+    return G == 0 ? 0 : search_core(e, nullptr, G);
+}
+
 extern "C" int oaz_search(oaz_engine* e, const oaz_state* roots, int G, oaz_move* out_move, float* out_pi,
                           float* out_root_value, oaz_search_stats* stats) {
     if (!e || !roots || G < 0) return oaz_set_err(OAZ_ERR_ARG, "search: bad arguments");
@@ -1131,20 +1163,10 @@ extern "C" int oaz_search(oaz_engine* e, const oaz_state* roots, int G, oaz_move
     for (int i = 0; i < G; ++i)
         if (roots[i].to_move > 1) return oaz_set_err(OAZ_ERR_ARG, "search: root %d has to_move=%d", i, roots[i].to_move);
     OAZ_ON_DEVICE(e->device);
-    if (int rc = begin_budget(e)) return rc;
-    const TreeView t = tree_view(e, (uint32_t)G);
-    HIP_TRY(hipMemcpyAsync(e->s_roots, roots, (size_t)G * sizeof(oaz_state), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemsetAsync(e->stats, 0, (size_t)G * GS_COUNT * sizeof(uint64_t), e->stream));
-    std::vector<uint32_t> plies((size_t)G, e->search_calls);
-    HIP_TRY(hipMemcpyAsync(e->s_ply, plies.data(), (size_t)G * 4, hipMemcpyHostToDevice, e->stream));
-    e->search_calls++;
-    HIP_TRY(launch_tree_reset(t, e->stream));
-    if (int rc = run_sims(e, t, e->s_roots, nullptr, nullptr, e->s_ply)) {
-        (void)hipStreamSynchronize(e->stream);  // the plies upload reads this frame's vector
+    if (int rc = search_core(e, roots, G)) {
+        (void)hipStreamSynchronize(e->stream);  // the roots upload reads the caller's buffer
         return rc;
     }
-    if (int rc = timed(e, 3, (uint32_t)G, [&] { return launch_search_finalize(t, e->s_roots, e->s_move, e->s_pi, e->stream); }))
-        return rc;
     if (out_root_value) {  // extra root evaluation (alphazero_mcts/mod.rs:137-141)
         if (int rc = evaluate(e, e->s_roots, (uint32_t)G, e->s_rootp, e->s_rootv)) return rc;
         HIP_TRY(hipMemcpyAsync(out_root_value, e->s_rootv, (size_t)G * 4, hipMemcpyDeviceToHost, e->stream));

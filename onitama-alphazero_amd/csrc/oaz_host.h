@@ -140,6 +140,49 @@ struct Carver {
     }
 };
 
+// Page-locked host memory (hipHostMalloc): what an asynchronous copy may read or write while the host goes on.
+template <class T>
+class PinnedBuf {
+    T* p_ = nullptr;
+    size_t n_ = 0;
+
+public:
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : p_(o.p_), n_(o.n_) {
+        o.p_ = nullptr;
+        o.n_ = 0;
+    }
+    ~PinnedBuf() {
+        if (p_) (void)hipHostFree(p_);
+    }
+    int alloc(size_t count) {
+        if (p_) (void)hipHostFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+        void* q = nullptr;
+        HIP_TRY(hipHostMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 16, hipHostMallocDefault));
+        p_ = static_cast<T*>(q);
+        n_ = count;
+        return 0;
+    }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }
+    T& operator[](size_t i) const { return p_[i]; }
+};
+
+// Engine internals used by the arena (oaz_arena.hip): the search-mode buffers a device-resident fight writes
+// its roots to and reads its moves from, and the search of the G roots already in `roots` (enqueued on
+// `stream`, the caller being on the engine's device; the moves are then in `moves`).
+struct oaz_arena_engine_view {
+    int device;
+    uint32_t games;
+    oaz_state* roots;
+    oaz_move* moves;
+    hipStream_t stream;
+};
+int oaz_engine_arena_view(oaz_engine* e, oaz_arena_engine_view* out);
+int oaz_engine_search_resident(oaz_engine* e, int G);
+
 // Engine internals used by the communicator (oaz_comm.cpp).
 int oaz_engine_samples_peek(oaz_engine* e, const oaz_sample** dev, size_t* n, int* device);
 int oaz_engine_samples_consume(oaz_engine* e, size_t n);

@@ -14,6 +14,7 @@ from .mcts import (AlphaZeroMcts, AlphaZeroMctsConfig, ConvResNet, ConvResNetCon
 from .selfplay import SelfPlayData, TrainConfig, self_play
 from .evaluator import (AlphaZeroAgent, EloRating, Evaluator, EvaluatorConfig, FightStatistics, PitStatistics,
                         RandomAgent, fight)
+from .arena import NativeRandomAgent, native_fight
 from .pure_mcts import Mcts, pure_mcts_search
 from .alpha_beta import AlphaBeta, alpha_beta_search
 from .trainer import Trainer, train_epochs
@@ -25,5 +26,5 @@ __all__ = [
     "AlphaZeroMctsConfig", "ConvResNet", "ConvResNetConfig", "Options", "TrainingAlphaZeroMcts", "reward",
     "SelfPlayData", "TrainConfig", "self_play", "AlphaZeroAgent", "EloRating", "Evaluator", "EvaluatorConfig",
     "FightStatistics", "PitStatistics", "RandomAgent", "fight", "Mcts", "pure_mcts_search", "Trainer", "train_epochs",
-    "LoopConfig", "Stats", "train", "AlphaBeta", "alpha_beta_search",
+    "LoopConfig", "Stats", "train", "AlphaBeta", "alpha_beta_search", "NativeRandomAgent", "native_fight",
 ]

@@ -182,6 +182,51 @@ class oaz_alphabeta_stats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("positions", "max_positions_per_root", "roots_without_move")]
 
 
+AGENT_ALPHAZERO, AGENT_RANDOM, AGENT_PURE_MCTS, AGENT_ALPHABETA = 0, 1, 2, 3  # oaz_arena_agent.kind
+
+
+class oaz_arena_agent(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("reserved", C.c_int32),
+        ("engine", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("mcts", oaz_pure_mcts_config),
+        ("alphabeta", oaz_alphabeta_config),
+    ]
+
+
+class oaz_arena_config(C.Structure):
+    _fields_ = [
+        ("game_amnt", C.c_int32),
+        ("max_plies", C.c_int32),
+        ("fixed_deck", C.c_int32),
+        ("device", C.c_int32),
+        ("deck", C.c_uint8 * 5),
+        ("pad", C.c_uint8 * 3),
+        ("seed", C.c_uint64),
+        ("start", C.c_void_p),
+    ]
+
+
+class oaz_fight_stats(C.Structure):
+    _fields_ = [
+        ("rating_a", C.c_double),
+        ("rating_b", C.c_double),
+        ("winrate", C.c_double),
+        ("color_winrate", C.c_double * 2),
+        ("wins", C.c_uint32),
+        ("loses", C.c_uint32),
+        ("draws", C.c_uint32),
+        ("color_wins", C.c_uint32 * 2),
+        ("color_loses", C.c_uint32 * 2),
+        ("color_draws", C.c_uint32 * 2),
+        ("reserved", C.c_uint32),
+        ("plies_total", C.c_uint64),
+        ("passes", C.c_uint64),
+    ]
+
+
 class oaz_comm_id(C.Structure):
     _fields_ = [("internal", C.c_char * 128)]
 
@@ -204,6 +249,7 @@ assert C.sizeof(oaz_move) == 4
 assert C.sizeof(oaz_node) == 32
 assert C.sizeof(oaz_sample) == 228
 assert C.sizeof(oaz_config) == 120 and oaz_config.search_time_ns.offset == 104
+assert C.sizeof(oaz_arena_agent) == 88 and C.sizeof(oaz_arena_config) == 40 and C.sizeof(oaz_fight_stats) == 96
 
 STATE_DTYPE = np.dtype(
     [("kings", "<u4", 2), ("pawns", "<u4", 2), ("cards", "u1", 5), ("to_move", "u1"), ("pad", "u1", 2)]
@@ -287,6 +333,13 @@ _PROTOS = {
     "oaz_alphabeta_evaluate": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _VOIDP]),
     "oaz_alphabeta_search": (C.c_int, [_VOIDP, C.c_int, _P(oaz_alphabeta_config), _VOIDP, _VOIDP,
                                        _P(oaz_alphabeta_stats)]),
+    "oaz_arena_config_default": (None, [_P(oaz_arena_config)]),
+    "oaz_elo_change": (None, [C.c_double, C.c_double, C.c_int, _P(C.c_double), _P(C.c_double)]),
+    "oaz_fight_stats_fold": (C.c_int, [_VOIDP, C.c_int, C.c_double, C.c_double, _P(oaz_fight_stats), _VOIDP]),
+    "oaz_random_agent_move": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, _VOIDP, _VOIDP]),
+    "oaz_arena_capacity": (C.c_int, [_P(oaz_arena_config), _P(C.c_int32 * 2)]),
+    "oaz_arena_fight": (C.c_int, [_P(oaz_arena_config), _P(oaz_arena_agent), _P(oaz_arena_agent), C.c_double,
+                                  C.c_double, _P(oaz_fight_stats), _VOIDP, _VOIDP, _VOIDP]),
     "oaz_train_config_default": (None, [_P(oaz_train_config)]),
     "oaz_trainer_create": (_VOIDP, [_P(oaz_train_config), C.c_int]),
     "oaz_trainer_destroy": (None, [_VOIDP]),

@@ -246,7 +246,7 @@ class Evaluator:  # evaluator.rs:139-193
         self.config, self.best, self.new, self.ratings = config, best, new, ratings
 
     def pit(self, sims: int = 400, concurrent: bool = True, alphabeta: bool = False,
-            enforce_search_time: bool = True) -> Tuple[PitStatistics, bool]:
+            enforce_search_time: bool = True, native: bool = False) -> Tuple[PitStatistics, bool]:
         """evaluator.rs:169-193. The reference starts the fights on threads of their own, each with
         its own copy of the networks (`VarStore::copy`, evaluator.rs:206-231); here each fight gets
         weight copies too, so every fight searches on engines of its own and the fights run at the
@@ -260,7 +260,16 @@ class Evaluator:  # evaluator.rs:139-193
         fifth network copy against AlphaBeta{max_depth 4, 400 ms}, rated by ratings[3] when given (else
         800 / 800), run and released like the other three. Off by default: the three fights above are then
         exactly what they were. enforce_search_time=False runs every network search to exactly `sims`
-        playouts whatever the clock says (AlphaZeroMctsConfig.enforce_search_time), for runs that are compared."""
+        playouts whatever the clock says (AlphaZeroMctsConfig.enforce_search_time), for runs that are compared.
+
+        native=True plays every fight on the device through oaz_arena_fight (arena.native_fight), on the same
+        threads and weight copies; the random opponent is then arena.NativeRandomAgent(config.seed), whose draws
+        are keyed by (game, ply) instead of numpy's stream, so the random fight's games differ from the
+        default's while the other fights' are the same."""
+        play, random_agent = fight, RandomAgent
+        if native:
+            from .arena import NativeRandomAgent, native_fight
+            play, random_agent = native_fight, NativeRandomAgent
         cfg = AlphaZeroMctsConfig(search_time=0.4, max_playouts=sims, train=False,  # evaluator.rs:198-204
                                   enforce_search_time=enforce_search_time)
         from .pure_mcts import Mcts  # evaluator.rs:314-353: Mcts{400 ms, min visits 5, c 1.41, 400 playouts}
@@ -270,22 +279,22 @@ class Evaluator:  # evaluator.rs:139-193
 
         models = [copy(self.new), copy(self.best), copy(self.new), copy(self.new)]
         fights = [
-            lambda: fight(self.config, AlphaZeroAgent(cfg, models[0]), AlphaZeroAgent(cfg, models[1]),
-                          *self.ratings[0]),
-            lambda: fight(self.config, AlphaZeroAgent(cfg, models[2]), RandomAgent(self.config.seed),
-                          *self.ratings[1]),
-            lambda: fight(self.config, AlphaZeroAgent(cfg, models[3]),
-                          Mcts(search_time=0.4, min_node_visits=5, exploration_c=1.41, max_playouts=sims,
-                               seed=self.config.seed, device=self.new.options.device), *self.ratings[2]),
+            lambda: play(self.config, AlphaZeroAgent(cfg, models[0]), AlphaZeroAgent(cfg, models[1]),
+                         *self.ratings[0]),
+            lambda: play(self.config, AlphaZeroAgent(cfg, models[2]), random_agent(self.config.seed),
+                         *self.ratings[1]),
+            lambda: play(self.config, AlphaZeroAgent(cfg, models[3]),
+                         Mcts(search_time=0.4, min_node_visits=5, exploration_c=1.41, max_playouts=sims,
+                              seed=self.config.seed, device=self.new.options.device), *self.ratings[2]),
         ]
         owned = [[models[0], models[1]], [models[2]], [models[3]]]  # each fight's network copies
         if alphabeta:
             from .alpha_beta import AlphaBeta  # evaluator.rs:303-306: AlphaBeta{max_depth 4, 400 ms}
             models.append(copy(self.new))
             ab_ratings = self.ratings[3] if len(self.ratings) > 3 else (800.0, 800.0)
-            fights.append(lambda: fight(self.config, AlphaZeroAgent(cfg, models[4]),
-                                        AlphaBeta(max_depth=4, search_time=0.4, device=self.new.options.device),
-                                        *ab_ratings))
+            fights.append(lambda: play(self.config, AlphaZeroAgent(cfg, models[4]),
+                                       AlphaBeta(max_depth=4, search_time=0.4, device=self.new.options.device),
+                                       *ab_ratings))
             owned.append([models[4]])
 
         def release(ms):  # a fight's engines (the reference drops each fight's VarStores)

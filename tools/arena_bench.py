@@ -1,0 +1,178 @@
+#!/usr/bin/env python3
+"""`evaluator.fight` (the Python loop) beside `arena.native_fight` (oaz_arena_fight, states resident on the
+device) on one GPU, in one process. Measurement tool; bench.py is the flagship's and is not touched.
+
+Agent: the trained 3-block network; opponent: a random-init one, the Random agent or alpha-beta (max_depth 4);
+400 simulations per move, random deals, max_plies 150, no search_time budget. Cases:
+  az_vs_az 4 096 games, az_vs_random 4 096 and 65 536 games, az_vs_alphabeta 4 096 games.
+
+Method: per case one warm-up of each kind, then `--reps` (5) timed runs of each, alternating python / native,
+with the host's monotonic clock around the whole call; the median is reported with the minimum and maximum
+(the spread). The Random opponents differ by construction (numpy's stream against Philox keyed by game and
+ply), so those two fights play different games of the same kind; the others play the same games, which the
+tool checks.
+
+Per-ply host time outside the searches:
+  python: wall time of the fight minus the union of the intervals in which an agent's generate_moves_np ran
+          (the two sides' searches of a ply overlap), over the fight's plies (its longest game);
+  native: the searches are enqueued inside one C call, so this is measured by a fight of the same size whose two
+          sides are both the Random agent: routing, one trivial kernel per side, the move application and the
+          8-byte read-back per ply, over that fight's plies.
+
+usage: python tools/arena_bench.py [--out profiles/arena_native_<date>.json] [--reps 5] [--sims 400]
+                                   [--cases az_vs_az:4096,az_vs_random:4096,az_vs_random:65536,az_vs_alphabeta:4096]"""
+from __future__ import annotations
+
+import argparse
+import datetime
+import json
+import statistics
+import sys
+import threading
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "onitama-alphazero_amd"))
+
+from onitama_az import _abi  # noqa: E402
+from onitama_az.alpha_beta import AlphaBeta  # noqa: E402
+from onitama_az.arena import NativeRandomAgent, native_fight  # noqa: E402
+from onitama_az.evaluator import AlphaZeroAgent, EvaluatorConfig, RandomAgent, fight  # noqa: E402
+from onitama_az.mcts import AlphaZeroMctsConfig, ConvResNet, ConvResNetConfig  # noqa: E402
+
+
+class Clocked:
+    """A BatchedAgent whose generate_moves_np intervals are recorded (shared list, both sides)."""
+
+    def __init__(self, inner, log, lock):
+        self.inner, self.log, self.lock = inner, log, lock
+
+    def reserve(self, n):
+        self.inner.reserve(n)
+
+    def device_key(self):
+        return getattr(self.inner, "device_key", lambda: None)()
+
+    def name(self):
+        return self.inner.name()
+
+    def generate_moves_np(self, roots):
+        t0 = time.perf_counter()
+        out = self.inner.generate_moves_np(roots)
+        with self.lock:
+            self.log.append((t0, time.perf_counter()))
+        return out
+
+
+def union_length(intervals):
+    total, end = 0.0, float("-inf")
+    for a, b in sorted(intervals):
+        if a > end:
+            total += b - a
+            end = b
+        elif b > end:
+            total += b - end
+            end = b
+    return total
+
+
+def spread(ts):
+    return {"median_s": statistics.median(ts), "min_s": min(ts), "max_s": max(ts), "runs_s": [round(t, 4) for t in ts]}
+
+
+def run_case(kind: str, games: int, sims: int, reps: int, nets) -> dict:
+    cfg = EvaluatorConfig(game_amnt=games, max_plies=150, seed=3)
+    mcfg = AlphaZeroMctsConfig(max_playouts=sims, train=False, enforce_search_time=False)
+
+    def sides(native: bool):
+        agent = AlphaZeroAgent(mcfg, nets[0])
+        if kind == "az_vs_az":
+            return agent, AlphaZeroAgent(mcfg, nets[1])
+        if kind == "az_vs_random":
+            return agent, (NativeRandomAgent(cfg.seed) if native else RandomAgent(cfg.seed))
+        if kind == "az_vs_alphabeta":
+            return agent, AlphaBeta(max_depth=4)
+        raise SystemExit(f"unknown case {kind}")
+
+    def python_run():
+        log, lock = [], threading.Lock()
+        a, b = sides(False)
+        t0 = time.perf_counter()
+        st = fight(cfg, Clocked(a, log, lock), Clocked(b, log, lock))
+        dt = time.perf_counter() - t0
+        return st, dt, (dt - union_length(log)) / max(st.plies)
+
+    def native_run():
+        a, b = sides(True)
+        t0 = time.perf_counter()
+        st = native_fight(cfg, a, b)
+        return st, time.perf_counter() - t0
+
+    py_st, _, _ = python_run()  # warm-up of each kind: engines, kernels, thread pool
+    nat_st, _ = native_run()
+    py_t, py_host, nat_t = [], [], []
+    for _ in range(reps):  # alternating, same process
+        py_st, dt, host = python_run()
+        py_t.append(dt)
+        py_host.append(host)
+        nat_st, dt = native_run()
+        nat_t.append(dt)
+        print(f"# {kind} {games}: python {py_t[-1]:.3f} s, native {nat_t[-1]:.3f} s", flush=True)
+    # the arena's own per-ply cost at this size: a fight without searches
+    rr = [NativeRandomAgent(1), NativeRandomAgent(2)]
+    native_fight(cfg, *rr)
+    t0 = time.perf_counter()
+    rr_st = native_fight(cfg, *rr)
+    rr_dt = time.perf_counter() - t0
+    row = {"case": kind, "games": games, "sims": sims, "reps": reps,
+           "python": {**spread(py_t), "games_per_s": games / statistics.median(py_t),
+                      "host_outside_searches_per_ply_ms": 1e3 * statistics.median(py_host), "plies_max": max(py_st.plies),
+                      "wins": py_st.general.wins, "loses": py_st.general.loses, "draws": py_st.general.draws},
+           "native": {**spread(nat_t), "games_per_s": games / statistics.median(nat_t),
+                      "per_ply_without_searches_ms": 1e3 * rr_dt / max(rr_st.plies),
+                      "random_vs_random_fight_s": rr_dt, "random_vs_random_plies_max": max(rr_st.plies),
+                      "plies_max": max(nat_st.plies), "passes": nat_st.passes,
+                      "wins": nat_st.general.wins, "loses": nat_st.general.loses, "draws": nat_st.general.draws},
+           "native_over_python_time": statistics.median(nat_t) / statistics.median(py_t)}
+    if kind != "az_vs_random":
+        row["same_games"] = bool(py_st.results == nat_st.results and py_st.plies == nat_st.plies)
+    return row
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=str(ROOT / "profiles" / f"arena_native_{datetime.date.today():%Y%m%d}.json"))
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sims", type=int, default=400)
+    ap.add_argument("--cases", default="az_vs_az:4096,az_vs_random:4096,az_vs_random:65536,az_vs_alphabeta:4096")
+    args = ap.parse_args()
+    if _abi.device_count() == 0:
+        raise SystemExit("no GPU: this tool measures on one")
+    trained = np.load(ROOT / "tests" / "golden" / "weights_3block_trained.npy")
+    nets = (ConvResNet(ConvResNetConfig(resnet_block_amnt=3), weights=trained),
+            ConvResNet(ConvResNetConfig(resnet_block_amnt=3), seed=7))
+    out = {"tool": "tools/arena_bench.py", "date": f"{datetime.date.today():%Y-%m-%d}",
+           "clock": "time.perf_counter around evaluator.fight / arena.native_fight (engines already created by the "
+                    "warm-up); one process, runs alternating python / native",
+           "agent": "trained 3-block network", "max_plies": 150, "cases": []}
+    path = Path(args.out)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    if path.exists():  # cases measured by an earlier call stay (a long case may run in a call of its own)
+        old = json.loads(path.read_text())
+        if old.get("tool") == out["tool"]:
+            out["cases"] = old.get("cases", [])
+    for spec in args.cases.split(","):
+        kind, games = spec.split(":")
+        row = run_case(kind, int(games), args.sims, args.reps, nets)
+        out["cases"] = [c for c in out["cases"] if (c["case"], c["games"]) != (kind, int(games))] + [row]
+        print(json.dumps(row), flush=True)
+        path.write_text(json.dumps(out, indent=1) + "\n")
+    print("wrote", args.out)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
