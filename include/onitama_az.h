@@ -563,6 +563,48 @@ int oaz_alphabeta_evaluate(const oaz_state* s, const uint8_t* move_result, int n
 int oaz_alphabeta_search(const oaz_state* roots, int G, const oaz_alphabeta_config* cfg,
                          oaz_move* out_move, int32_t* out_score, oaz_alphabeta_stats* stats);
 
+/* Agent::generate_move (mod.rs:136-170) with its clock and up to the tournament's max_depth 8
+ * (bin/tournament.rs:107-110), as a split search: the first `split` plies of every root are laid out as levels
+ * of nodes in move order, every node of the last level (an "item") is searched by one GPU lane with the full
+ * window and the plies that remain, and the exact values are folded back up with the reference's strict
+ * comparisons. Moves and scores equal oaz_alphabeta_search's (and the sequential search's) at every split;
+ * only the positions visited differ (about 1.7x, 3.8x, 5.9x the sequential search's at split 1, 2, 3). */
+typedef struct oaz_alphabeta_agent_config {
+    int32_t max_depth;       /* 2..8 (tournament.rs:107-110 uses 8) */
+    int32_t device;
+    int64_t search_time_ns;  /* 0 = off: the one search to max_depth - 1 plies (as oaz_alphabeta_search) */
+    int32_t split;           /* 0 = auto (from G and the plies), 1..3; clamped to plies - 1, at least 1 */
+    int32_t reserved[3];
+} oaz_alphabeta_agent_config; /* 32 bytes */
+
+typedef struct oaz_alphabeta_agent_stats {
+    uint64_t positions, max_positions_per_root, roots_without_move; /* as oaz_alphabeta_stats, last iteration */
+    uint64_t items;          /* frontier items searched, last iteration */
+    int32_t iterations;      /* iterations run */
+    int32_t plies;           /* plies of the last iteration: the result is that search's */
+    int32_t split;           /* S used by the last iteration */
+    int32_t reserved;
+    double elapsed_ms;       /* the whole call on the host's monotonic clock */
+} oaz_alphabeta_agent_stats; /* 56 bytes */
+
+void oaz_alphabeta_agent_config_default(oaz_alphabeta_agent_config* cfg);   /* max_depth 6, device 0, 1 s, auto split */
+/* One answer per root (colour = root.to_move), out_move / out_score / the pass move as oaz_alphabeta_search's.
+ * The clock is the reference's loop (mod.rs:145-156): iteration d = 1, 2, .. (a search to d plies) starts only
+ * while d < max_depth and the time since the call began is below search_time_ns; the time is read on the host
+ * between iterations, a started iteration is never abandoned, and the result is the last iteration's. The
+ * first iteration always runs (defined here: the reference unwraps None when the clock has run out before
+ * it). The G roots of a call share the clock and all reach the same depth (stats->plies), so a large batch
+ * under a short search_time_ns is searched less deeply than one root would be (as oaz_config.search_time_ns).
+ * With search_time_ns == 0 only the last iteration runs, because iterations carry nothing over.
+ * Runs on cfg->device on a stream of its own with buffers allocated and freed per call (49 B per node of
+ * the split levels; the roots of a large call are searched a few at a time so that a launch holds about 4 M
+ * items); the calling thread's current HIP device is restored before the call returns. OAZ_ERR_ARG, checked
+ * before any device is touched: a null pointer, max_depth outside 2..8, split outside 0..3, a negative
+ * search_time_ns, a root that is not a valid state. An explicit split that puts more than 2^27 nodes on one
+ * level is OAZ_ERR_CAPACITY. */
+int oaz_alphabeta_generate_move(const oaz_state* roots, int G, const oaz_alphabeta_agent_config* cfg,
+                                oaz_move* out_move, int32_t* out_score, oaz_alphabeta_agent_stats* stats);
+
 /* ---- arena: a fight played on the device (Evaluator, alphazero-training/src/evaluator.rs) -----------
  * fight (evaluator.rs:355-399) with all game_amnt games advanced together and their states resident on the
  * GPU: every ply the active games are routed to the side that moves in them (ascending game index), each

@@ -182,6 +182,17 @@ class oaz_alphabeta_stats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("positions", "max_positions_per_root", "roots_without_move")]
 
 
+class oaz_alphabeta_agent_config(C.Structure):  # 32 bytes
+    _fields_ = [("max_depth", C.c_int32), ("device", C.c_int32), ("search_time_ns", C.c_int64), ("split", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class oaz_alphabeta_agent_stats(C.Structure):  # 56 bytes
+    _fields_ = [("positions", C.c_uint64), ("max_positions_per_root", C.c_uint64), ("roots_without_move", C.c_uint64),
+                ("items", C.c_uint64), ("iterations", C.c_int32), ("plies", C.c_int32), ("split", C.c_int32),
+                ("reserved", C.c_int32), ("elapsed_ms", C.c_double)]
+
+
 AGENT_ALPHAZERO, AGENT_RANDOM, AGENT_PURE_MCTS, AGENT_ALPHABETA = 0, 1, 2, 3  # oaz_arena_agent.kind
 
 
@@ -333,6 +344,9 @@ _PROTOS = {
     "oaz_alphabeta_evaluate": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _VOIDP]),
     "oaz_alphabeta_search": (C.c_int, [_VOIDP, C.c_int, _P(oaz_alphabeta_config), _VOIDP, _VOIDP,
                                        _P(oaz_alphabeta_stats)]),
+    "oaz_alphabeta_agent_config_default": (None, [_P(oaz_alphabeta_agent_config)]),
+    "oaz_alphabeta_generate_move": (C.c_int, [_VOIDP, C.c_int, _P(oaz_alphabeta_agent_config), _VOIDP, _VOIDP,
+                                              _P(oaz_alphabeta_agent_stats)]),
     "oaz_arena_config_default": (None, [_P(oaz_arena_config)]),
     "oaz_elo_change": (None, [C.c_double, C.c_double, C.c_int, _P(C.c_double), _P(C.c_double)]),
     "oaz_fight_stats_fold": (C.c_int, [_VOIDP, C.c_int, C.c_double, C.c_double, _P(oaz_fight_stats), _VOIDP]),

@@ -26,6 +26,25 @@ class NativeRandomAgent:
     def name(self) -> str:
         return "Random AI"
 
+    # In `evaluator.fight` (the host loop) the same draws come from the host-only oaz_random_agent_move: fight
+    # names the games and their plies of the coming batch through begin_turn.
+    def reserve(self, n: int) -> None:
+        pass
+
+    def begin_turn(self, games, plies) -> None:
+        self._turn = (np.asarray(games, dtype=np.uint64), np.asarray(plies, dtype=np.uint32))
+
+    def generate_moves_np(self, roots: np.ndarray) -> np.ndarray:
+        roots = np.ascontiguousarray(roots, dtype=_abi.STATE_DTYPE).reshape(-1)
+        games, plies = self._turn
+        assert len(games) == len(roots), "begin_turn names the games of this batch"
+        out = np.zeros(len(roots), dtype=_abi.MOVE_DTYPE)
+        lib = _abi.load()
+        for i in range(len(roots)):
+            _abi.check(lib.oaz_random_agent_move(int(self.seed), int(games[i]), int(plies[i]), _abi.ptr(roots[i:i + 1]),
+                                                 _abi.ptr(out[i:i + 1])))
+        return out
+
 
 def arena_config(config: EvaluatorConfig, device: int = 0) -> _abi.oaz_arena_config:
     c = _abi.oaz_arena_config()

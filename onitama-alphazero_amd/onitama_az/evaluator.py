@@ -220,6 +220,9 @@ def fight(config: EvaluatorConfig, agent: BatchedAgent, opponent: BatchedAgent, 
             agent_moves = active & (red_to_move == agent_red)
             turns = [(np.where(who)[0], ag) for who, ag in ((agent_moves, agent), (active & ~agent_moves, opponent))]
             turns = [(idx, ag) for idx, ag in turns if len(idx)]
+            for idx, ag in turns:  # an agent whose answer depends on the game and its ply (arena.NativeRandomAgent)
+                if hasattr(ag, "begin_turn"):
+                    ag.begin_turn(idx, plies[idx])
             if concurrent and len(turns) == 2:
                 futs = [pool.submit(ag.generate_moves_np, np.ascontiguousarray(states[idx])) for idx, ag in turns]
                 moves = [f.result() for f in futs]

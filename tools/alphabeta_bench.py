@@ -11,7 +11,13 @@ Method: every shape is warmed up, then timed `--reps` times with the host's mono
 call (upload, launch, stream synchronise, download; the call returns after its stream is idle), and the
 median is reported with the minimum and maximum. Writes one JSON file.
 
-usage: python tools/alphabeta_bench.py [--out profiles/alphabeta_<date>.json] [--reps 7] [--pit GAMES]
+usage: python tools/alphabeta_bench.py [--out profiles/alphabeta_<date>.json] [--reps 7] [--pit GAMES] [--deep]
+  --deep measures the split search instead (oaz_alphabeta_generate_move, untimed; profiles/alphabeta_deep_<date>.json),
+  by the same method: one mid-game root per call (the latency roots above) at max_depth 6 and 8 for split 1, 2, 3
+  and auto, oaz_alphabeta_search at max_depth 6 and the one-thread restatement on the same roots, 4 096 roots at
+  max_depth 4 on both paths, with the items, positions and elapsed_ms of each; and the positions per second one
+  lane sustains, from the split-1 max_depth-8 calls (the call lasts as long as its longest item, whose positions
+  the restatement counts from that root child).
   --pit GAMES also times Evaluator.pit(alphabeta=True) against pit(alphabeta=False) at game_amnt = GAMES
   (as tools/pit_timing.py: trained 3-block network vs a random one, concurrent fights)."""
 from __future__ import annotations
@@ -105,17 +111,112 @@ def cpu_rate(ref, roots: np.ndarray, max_depth: int, threads: int):
             "positions_per_s": float(pos.sum()) / dt}, mv, sc
 
 
+def cpu_one(ref, root: np.ndarray, max_depth: int):
+    """(seconds, positions) of the restatement's search of one root on this thread."""
+    mv = np.zeros(1, dtype=_abi.MOVE_DTYPE)
+    sc = np.zeros(1, dtype=np.int32)
+    pos = np.zeros(1, dtype=np.int64)
+    t0 = time.perf_counter()
+    rc = ref.abref_search_batch(_abi.ptr(root), 1, max_depth, _abi.ptr(mv), _abi.ptr(sc), _abi.ptr(pos))
+    dt = time.perf_counter() - t0
+    assert rc == 0
+    return dt, int(pos[0]), mv, sc
+
+
+def longest_item(ref, root: np.ndarray, max_depth: int) -> int:
+    """Positions of the longest item of a split-1 search of `root`: a lane walks a root child's subtree as the
+    sequential search does from that child, so the restatement from the child to max_depth - 1 counts the same
+    positions (a child reached by a winning move is one position)."""
+    moves, counts = movegen_batch(root)
+    n = int(counts[0])
+    kids = np.ascontiguousarray(np.repeat(root, n))
+    res = step_batch(kids, np.ascontiguousarray(moves[0, :n]))  # (to_move switches)
+    return max(1 if res[k] in (_abi.RED_WIN, _abi.BLUE_WIN) else cpu_one(ref, kids[k:k + 1], max_depth - 1)[1]
+               for k in range(n))
+
+
+def deep(args, ref) -> int:
+    """The split search (oaz_alphabeta_generate_move) beside oaz_alphabeta_search and the restatement: one mid-game
+    root per call at max_depth 6 and 8 for split 1, 2, 3 and auto, and 4 096 roots at max_depth 4 on both paths."""
+    from onitama_az.alpha_beta import alpha_beta_generate_move
+    pool = midgame_roots(65536, 7201)  # the roots of latency_max_depth6_one_midgame_root (alphabeta_<date>.json)
+    n_lat = args.deep_roots
+    out = {"tool": "tools/alphabeta_bench.py --deep", "date": f"{datetime.date.today():%Y-%m-%d}",
+           "clock": "time.perf_counter around the whole call (upload, every launch and read-back of the levels, "
+                    "download, per-call hipMalloc/hipFree and stream create/destroy); elapsed_ms is the call's own",
+           "reps": args.reps, "warmup": 2, "one_midgame_root": [], "batch_4096_max_depth4": []}
+    alpha_beta_generate_move(pool[:1], max_depth=4)
+    for depth in (6, 8):
+        cpu = [cpu_one(ref, np.ascontiguousarray(pool[i:i + 1]), depth) for i in range(n_lat)] if ref is not None else None
+        paths = [("generate_move", s) for s in (1, 2, 3, 0)] + ([("search", None)] if depth == 6 else [])
+        for path, split in paths:
+            rows = []
+            for i in range(n_lat):
+                one = np.ascontiguousarray(pool[i:i + 1])
+                if path == "search":
+                    r, t = timed(lambda: alpha_beta_search(one, max_depth=depth), 2, args.reps)
+                    row = {**t, "positions": int(r.stats.positions)}
+                else:
+                    r, t = timed(lambda: alpha_beta_generate_move(one, max_depth=depth, split=split), 2, args.reps)
+                    row = {**t, "positions": int(r.stats.positions), "items": int(r.stats.items),
+                           "split_used": int(r.stats.split), "elapsed_ms": float(r.stats.elapsed_ms)}
+                    if cpu is not None:
+                        row["equal_to_cpu"] = bool(r.moves.tobytes() == cpu[i][2].tobytes() and r.scores[0] == cpu[i][3][0])
+                    if split == 1 and depth == 8 and ref is not None:  # few lanes, each long: the per-lane rate
+                        row["longest_item_positions"] = longest_item(ref, one, depth)
+                        row["lane_positions_per_s"] = row["longest_item_positions"] / t["median_s"]
+                if cpu is not None:
+                    row.update(cpu1_s=cpu[i][0], cpu1_positions=cpu[i][1], x_cpu1=cpu[i][0] / t["median_s"])
+                rows.append(row)
+            sec = {"max_depth": depth, "path": path, "split": split, "roots": rows,
+                   "median_of_medians_s": statistics.median(x["median_s"] for x in rows),
+                   "min_of_medians_s": min(x["median_s"] for x in rows),
+                   "max_of_medians_s": max(x["median_s"] for x in rows)}
+            if cpu is not None:
+                sec["cpu1_median_s"] = statistics.median(c[0] for c in cpu)
+                sec["x_cpu1_median"] = sec["cpu1_median_s"] / sec["median_of_medians_s"]
+            if "lane_positions_per_s" in rows[0]:
+                sec["lane_positions_per_s_median"] = statistics.median(x["lane_positions_per_s"] for x in rows)
+            out["one_midgame_root"].append(sec)
+            print(json.dumps({k: v for k, v in sec.items() if k != "roots"}), flush=True)
+    roots = np.ascontiguousarray(pool[:4096])
+    for path, fn in (("search", lambda: alpha_beta_search(roots, max_depth=4)),
+                     ("generate_move", lambda: alpha_beta_generate_move(roots, max_depth=4))):
+        r, t = timed(fn, 2, args.reps)
+        row = {"path": path, "G": 4096, "max_depth": 4, **t, "roots_per_s": 4096 / t["median_s"],
+               "positions": int(r.stats.positions)}
+        if path == "generate_move":
+            row.update(items=int(r.stats.items), split_used=int(r.stats.split), elapsed_ms=float(r.stats.elapsed_ms))
+        out["batch_4096_max_depth4"].append(row)
+        print(json.dumps(row), flush=True)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
+    print("wrote", args.out)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / f"alphabeta_{datetime.date.today():%Y%m%d}.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--cpu-roots", type=int, default=4096)
     ap.add_argument("--pit", type=int, default=0)
     ap.add_argument("--pit-sims", type=int, default=400)
+    ap.add_argument("--deep", action="store_true", help="measure the split search (profiles/alphabeta_deep_<date>.json)")
+    ap.add_argument("--deep-roots", type=int, default=8)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / f"alphabeta_{'deep_' if args.deep else ''}{datetime.date.today():%Y%m%d}.json")
     if _abi.device_count() == 0:
         raise SystemExit("no GPU: this tool measures on one")
     import make_alphabeta_kats as gen
+    if args.deep:
+        with tempfile.TemporaryDirectory() as tmp:
+            ref = gen.build_ref(Path(tmp))
+            if ref is not None:
+                ref.abref_search_batch.restype = C.c_int
+                ref.abref_search_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            return deep(args, ref)
     with tempfile.TemporaryDirectory() as tmp:
         ref = gen.build_ref(Path(tmp))
         if ref is not None:
