@@ -696,6 +696,53 @@ int oaz_arena_fight(const oaz_arena_config* cfg, const oaz_arena_agent* agent, c
                     double agent_rating, double opponent_rating, oaz_fight_stats* stats, uint8_t* results,
                     int32_t* plies, double* history);
 
+/* ---- arena: a fight of any size on a fixed pool of refilled game slots ---------------------------------
+ * oaz_arena_fight with S = min(slots, game_amnt) game slots instead of one per game, so that an ALPHAZERO side's
+ * engine holds trees for S slots, not for game_amnt games, and late plies do not search ever smaller batches.
+ * The schedule, with `next` the first game not dealt yet:
+ *   1. slot i < S starts game i; next = S;
+ *   2. a round routes the active slots to the side that moves in them (ascending slot index), each side with
+ *      at least one root answers its batch in one search, and the moves are applied, as in oaz_arena_fight;
+ *   3. before the next round's route every slot that finished stores its result (last MoveResult, plies,
+ *      passes) under its game index;
+ *   4. the finished slots then take games next, next + 1, ... in ascending slot index while next < game_amnt:
+ *      the game's start position (oaz_deal_deck(seed, k) + oaz_initial_state, the fixed deck, or start[k]),
+ *      budget max_plies, no plies or passes made;
+ *   5. a finished slot that gets no game stays empty and is not harvested again;
+ *   6. the fight ends when a route finds no root for either side.
+ * Every active slot moves exactly once per round, so `rounds` is a function of the games' lengths and S alone.
+ * Results, plies and history are indexed by game and Elo is folded in game order, as in oaz_arena_fight. Extra
+ * device memory: 33 B per game (start state 24, result 1 + 4 + 4).
+ * Equalities: with slots >= game_amnt nothing is refilled and the call is oaz_arena_fight ply for ply, the
+ * pure-MCTS streams included. With fewer slots, a side whose answer depends only on the position (ALPHAZERO
+ * with root noise off, ALPHABETA without a clock) or on (game, ply) (RANDOM) plays every game as in
+ * oaz_arena_fight, so results, plies and statistics are equal game for game. Not equal: an ALPHAZERO side with
+ * root noise on (the noise is keyed by the engine's search count, so by the schedule) or stopped by its
+ * search_time (one clock per batch), and a PURE_MCTS side, which keeps the stream rule with "slot" for "game":
+ * game_id0 = c << 20 for the side's c-th search of the fight, root g being the side's g-th root in ascending slot
+ * index. That fight is still deterministic. The rollout generator's game word is 32 bits, so a PURE_MCTS side's
+ * streams recur after 4 096 searches of one fight. */
+typedef struct oaz_arena_slots_stats {
+    uint64_t rounds;        /* loop iterations in which at least one game moved */
+    uint64_t searches[2];   /* rounds in which the agent / the opponent had at least one root */
+    uint32_t max_batch[2];  /* the largest batch each side answered */
+    uint32_t slots;         /* slots used: min(slots, game_amnt) */
+    uint32_t reserved;
+} oaz_arena_slots_stats; /* 40 bytes */
+
+/* oaz_arena_capacity for a fight on `slots` slots: its values for slots >= game_amnt, else out[0] = out[1] =
+ * slots (slots at different plies can all be one side's turn). An ALPHAZERO side's engine needs at least that
+ * many `games`. slots < 1 is OAZ_ERR_ARG. Host only. */
+int oaz_arena_slots_capacity(const oaz_arena_config* cfg, int32_t slots, int32_t out[2]);
+/* oaz_arena_fight on a pool of slots (above): the same arguments with the same meaning and the same checks
+ * before any device is touched, with oaz_arena_slots_capacity for oaz_arena_capacity; in addition slots < 1 is
+ * OAZ_ERR_ARG. slot_stats is optional. game_amnt == 0 returns empty statistics and rounds == 0 without touching
+ * a device. */
+int oaz_arena_fight_slots(const oaz_arena_config* cfg, int32_t slots, const oaz_arena_agent* agent,
+                          const oaz_arena_agent* opponent, double agent_rating, double opponent_rating,
+                          oaz_fight_stats* stats, uint8_t* results, int32_t* plies, double* history,
+                          oaz_arena_slots_stats* slot_stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,9 @@
 //     k_arena_random, both asynchronously on the side's stream, so the two sides of a ply overlap; pure-MCTS
 //     and alpha-beta sides go through their host-pointer entry points with pinned staging buffers;
 //   * k_arena_apply runs on the side's stream right after its search (the sides' games are disjoint), and the
-//     next route waits for both sides' events.
+//     next route waits for both sides' events;
+//   * a fight on fewer slots than games (oaz_arena_fight_slots) runs k_arena_refill before every route: a slot
+//     that finished stores its result under its game index and is dealt the fight's next game.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -25,7 +27,8 @@
 
 using namespace oaz;
 
-static_assert(sizeof(oaz_arena_agent) == 88 && sizeof(oaz_arena_config) == 40 && sizeof(oaz_fight_stats) == 96,
+static_assert(sizeof(oaz_arena_agent) == 88 && sizeof(oaz_arena_config) == 40 && sizeof(oaz_fight_stats) == 96 &&
+                  sizeof(oaz_arena_slots_stats) == 40,
               "arena struct layout");
 
 namespace oaz {
@@ -153,6 +156,68 @@ __global__ void __launch_bounds__(kLaneBlock) k_arena_apply(Slots v, SideBuf sd,
     if (is_win(res) || left < 0) v.active[g] = 0;
 }
 
+// The games of a fight played on fewer slots than games (oaz_arena_fight_slots): where a game starts, where
+// its result goes when its slot has finished it, and the first game that no slot has been dealt yet.
+struct Games {
+    const oaz_state* start;  // [n] game k's start position
+    uint8_t* progress;       // [n] last MoveResult
+    int32_t* plies;          // [n] moves made
+    uint32_t* passes;        // [n] passes among them
+    uint32_t* next;          // [1] first game not dealt
+    uint32_t n;
+    int32_t max_plies;
+};
+constexpr uint64_t kNoGame = ~0ull;  // Slots::game of a slot that holds no game
+
+// Between two plies: every slot that finished its game stores the result under the game's index and is dealt
+// the fight's next game, in ascending slot order. One workgroup in k_arena_route's shape: each thread counts
+// the finished slots of its run, the scan of the runs ranks them, and the slot at rank r takes game next + r
+// while there is one; a slot that gets none is empty from then on (kNoGame) and never harvested again. Every
+// thread reads `next` before the scan's first barrier and the last thread writes it after the scan's last one.
+__global__ void __launch_bounds__(kRouteThreads) k_arena_refill(Slots v, Games gm) {
+    const uint32_t per = (v.n + kRouteThreads - 1) / kRouteThreads;
+    const uint32_t g0 = threadIdx.x * per < v.n ? threadIdx.x * per : v.n, g1 = g0 + per < v.n ? g0 + per : v.n;
+    const uint32_t next = *gm.next;
+    uint32_t sum = 0;
+    for (uint32_t g = g0; g < g1; ++g) sum += !v.active[g] && v.game[g] != kNoGame;
+    __shared__ uint32_t run[kRouteThreads];
+    run[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < kRouteThreads; d <<= 1) {  // inclusive Hillis-Steele scan of the runs
+        const uint32_t t = (int)threadIdx.x >= d ? run[threadIdx.x - d] : 0u;
+        __syncthreads();
+        run[threadIdx.x] += t;
+        __syncthreads();
+    }
+    uint64_t deal = (uint64_t)next + (run[threadIdx.x] - sum);  // the game this thread's next finished slot takes
+    for (uint32_t g = g0; g < g1; ++g) {
+        if (v.active[g]) continue;
+        const uint64_t k = v.game[g];
+        if (k == kNoGame) continue;
+        if (k < gm.n) {
+            gm.progress[k] = v.progress[g];
+            gm.plies[k] = v.plies[g];
+            gm.passes[k] = v.passes[g];
+        }
+        const uint64_t nk = deal++;
+        if (nk < gm.n) {
+            store_state(&v.state[g], load_state(&gm.start[nk]));
+            v.game[g] = nk;
+            v.plies[g] = 0;
+            v.budget[g] = gm.max_plies;
+            v.passes[g] = 0;
+            v.progress[g] = (uint8_t)OAZ_IN_PROGRESS;
+            v.active[g] = 1;
+        } else {
+            v.game[g] = kNoGame;
+        }
+    }
+    if (threadIdx.x == kRouteThreads - 1) {
+        const uint64_t nn = (uint64_t)next + run[kRouteThreads - 1];
+        *gm.next = nn < gm.n ? (uint32_t)nn : gm.n;
+    }
+}
+
 }  // namespace arena
 }  // namespace oaz
 
@@ -274,6 +339,15 @@ extern "C" int oaz_arena_capacity(const oaz_arena_config* cfg, int32_t out[2]) {
     return 0;
 }
 
+extern "C" int oaz_arena_slots_capacity(const oaz_arena_config* cfg, int32_t slots, int32_t out[2]) {
+    if (int rc = check_arena_config(cfg)) return rc;
+    if (slots < 1) return oaz_set_err(OAZ_ERR_ARG, "arena: slots %d", slots);
+    if (!out) return oaz_set_err(OAZ_ERR_ARG, "arena_slots_capacity: null output");
+    if (slots >= cfg->game_amnt) initial_states(cfg, nullptr, out);  // nothing is refilled: the lock-step fight's
+    else out[0] = out[1] = slots;  // slots at different plies can all be one side's turn
+    return 0;
+}
+
 // ---- the fight --------------------------------------------------------------------------------------------
 namespace {
 
@@ -375,11 +449,17 @@ int side_ply(Fight& f, const arena::Slots& v, Side& sd, int s, uint32_t cnt) {
     return 0;
 }
 
-int play(Fight& f, const arena::Slots& v, Side side[2], uint32_t* d_counts) {
+// gm (slots mode): finished slots are harvested and refilled before every route. ss (optional): the rounds' counts.
+int play(Fight& f, const arena::Slots& v, Side side[2], uint32_t* d_counts, const arena::Games* gm,
+         oaz_arena_slots_stats* ss) {
     const bool shared = side[1].staged != nullptr;
     for (;;) {
         arena::SideBuf b1 = side[1].buf;
         if (shared) b1.roots = side[1].staged;
+        if (gm) {
+            hipLaunchKernelGGL(arena::k_arena_refill, dim3(1), dim3(arena::kRouteThreads), 0, f.route, v, *gm);
+            HIP_TRY(hipGetLastError());
+        }
         hipLaunchKernelGGL(arena::k_arena_route, dim3(1), dim3(arena::kRouteThreads), 0, f.route, v, side[0].buf, b1, d_counts);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(f.counts.get(), d_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, f.route));
@@ -389,6 +469,13 @@ int play(Fight& f, const arena::Slots& v, Side side[2], uint32_t* d_counts) {
         for (int s = 0; s < 2; ++s)
             if (cnt[s] > side[s].buf.cap)
                 return oaz_set_err(OAZ_ERR_CAPACITY, "arena: %u roots for a side sized for %u", cnt[s], side[s].buf.cap);
+        if (ss) {
+            ss->rounds++;
+            for (int s = 0; s < 2; ++s) {
+                ss->searches[s] += cnt[s] != 0;
+                if (cnt[s] > ss->max_batch[s]) ss->max_batch[s] = cnt[s];
+            }
+        }
         // the sides whose work is only enqueued first, so a blocking side's search runs beside them
         for (int pass = 0; pass < 2; ++pass)
             for (int s = 0; s < 2; ++s)
@@ -397,17 +484,24 @@ int play(Fight& f, const arena::Slots& v, Side side[2], uint32_t* d_counts) {
     }
 }
 
-}  // namespace
-
-extern "C" int oaz_arena_fight(const oaz_arena_config* cfg, const oaz_arena_agent* agent, const oaz_arena_agent* opponent,
-                               double agent_rating, double opponent_rating, oaz_fight_stats* stats, uint8_t* results,
-                               int32_t* plies, double* history) {
+// Both entry points. slots == 0 is the lock-step fight: one slot per game and nothing beyond what it always
+// enqueued. Otherwise min(slots, game_amnt) slots, the per-game arrays and a refill before every route.
+int fight_on(const oaz_arena_config* cfg, int32_t slots, const oaz_arena_agent* agent, const oaz_arena_agent* opponent,
+             double agent_rating, double opponent_rating, oaz_fight_stats* stats, uint8_t* results, int32_t* plies,
+             double* history, oaz_arena_slots_stats* ss) {
     if (int rc = check_arena_config(cfg)) return rc;
     if (!stats) return oaz_set_err(OAZ_ERR_ARG, "arena: null stats");
-    const int n = cfg->game_amnt;
+    const bool pooled = slots > 0;
+    const int n = cfg->game_amnt;                   // games
+    const int m = pooled && slots < n ? slots : n;  // slots
+    if (ss) {
+        memset(ss, 0, sizeof(*ss));
+        ss->slots = (uint32_t)m;
+    }
     std::vector<oaz_state> start;
     int32_t need[2] = {0, 0};
     initial_states(cfg, &start, need);
+    if (m < n) need[0] = need[1] = m;  // (oaz_arena_slots_capacity)
     Side side[2];
     if (int rc = check_side("agent", agent, cfg, need[0], &side[0])) return rc;
     if (int rc = check_side("opponent", opponent, cfg, need[1], &side[1])) return rc;
@@ -421,17 +515,27 @@ extern "C" int oaz_arena_fight(const oaz_arena_config* cfg, const oaz_arena_agen
     const bool shared = side[0].ag.kind == OAZ_AGENT_ALPHAZERO && side[1].ag.kind == OAZ_AGENT_ALPHAZERO &&
                         side[0].ag.engine == side[1].ag.engine;
     arena::Slots v{};
-    v.n = (uint32_t)n;
+    v.n = (uint32_t)m;
+    arena::Games gm{};
+    gm.n = (uint32_t)n;
+    gm.max_plies = cfg->max_plies;
     uint32_t* d_counts = nullptr;
     auto carve = [&](Carver c) {
-        v.state = c.take<oaz_state>(n);
-        v.game = c.take<uint64_t>(n);
-        v.plies = c.take<int32_t>(n);
-        v.budget = c.take<int32_t>(n);
-        v.passes = c.take<uint32_t>(n);
-        v.progress = c.take<uint8_t>(n);
-        v.active = c.take<uint8_t>(n);
+        v.state = c.take<oaz_state>(m);
+        v.game = c.take<uint64_t>(m);
+        v.plies = c.take<int32_t>(m);
+        v.budget = c.take<int32_t>(m);
+        v.passes = c.take<uint32_t>(m);
+        v.progress = c.take<uint8_t>(m);
+        v.active = c.take<uint8_t>(m);
         d_counts = c.take<uint32_t>(2);
+        if (pooled) {
+            gm.start = c.take<oaz_state>(n);
+            gm.progress = c.take<uint8_t>(n);
+            gm.plies = c.take<int32_t>(n);
+            gm.passes = c.take<uint32_t>(n);
+            gm.next = c.take<uint32_t>(1);
+        }
         for (int s = 0; s < 2; ++s) {
             Side& sd = side[s];
             const bool az = sd.ag.kind == OAZ_AGENT_ALPHAZERO;
@@ -469,26 +573,32 @@ extern "C" int oaz_arena_fight(const oaz_arena_config* cfg, const oaz_arena_agen
         }
         return e;
     };
-    std::vector<uint64_t> ids((size_t)n);
-    for (int k = 0; k < n; ++k) ids[(size_t)k] = (uint64_t)k;
+    std::vector<uint64_t> ids((size_t)m);
+    for (int k = 0; k < m; ++k) ids[(size_t)k] = (uint64_t)k;
     std::vector<uint8_t> h_progress((size_t)n);
     std::vector<int32_t> h_plies((size_t)n);
     std::vector<uint32_t> h_passes((size_t)n);
     auto run = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(v.state, start.data(), (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, f.route));
-        HIP_TRY(hipMemcpyAsync(v.game, ids.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, f.route));
-        HIP_TRY(hipMemsetAsync(v.plies, 0, (size_t)n * 4, f.route));
-        HIP_TRY(hipMemsetAsync(v.passes, 0, (size_t)n * 4, f.route));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)v.budget, cfg->max_plies, (size_t)n, f.route));
-        HIP_TRY(hipMemsetAsync(v.progress, OAZ_IN_PROGRESS, (size_t)n, f.route));
-        HIP_TRY(hipMemsetAsync(v.active, 1, (size_t)n, f.route));
+        HIP_TRY(hipMemcpyAsync(v.state, start.data(), (size_t)m * sizeof(oaz_state), hipMemcpyHostToDevice, f.route));
+        HIP_TRY(hipMemcpyAsync(v.game, ids.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, f.route));
+        HIP_TRY(hipMemsetAsync(v.plies, 0, (size_t)m * 4, f.route));
+        HIP_TRY(hipMemsetAsync(v.passes, 0, (size_t)m * 4, f.route));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)v.budget, cfg->max_plies, (size_t)m, f.route));
+        HIP_TRY(hipMemsetAsync(v.progress, OAZ_IN_PROGRESS, (size_t)m, f.route));
+        HIP_TRY(hipMemsetAsync(v.active, 1, (size_t)m, f.route));
+        if (pooled) {  // slot i holds game i; the first game not dealt is m
+            HIP_TRY(hipMemcpyAsync(const_cast<oaz_state*>(gm.start), start.data(), (size_t)n * sizeof(oaz_state),
+                                   hipMemcpyHostToDevice, f.route));
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)gm.next, m, 1, f.route));
+        }
         // the engines' streams may still run earlier work that reads their root buffers
         for (int s = 0; s < 2; ++s)
             if (side[s].ag.kind == OAZ_AGENT_ALPHAZERO) HIP_TRY(hipStreamSynchronize(side[s].st));
-        if (int rc = play(f, v, side, d_counts)) return rc;
-        HIP_TRY(hipMemcpyAsync(h_progress.data(), v.progress, (size_t)n, hipMemcpyDeviceToHost, f.route));
-        HIP_TRY(hipMemcpyAsync(h_plies.data(), v.plies, (size_t)n * 4, hipMemcpyDeviceToHost, f.route));
-        HIP_TRY(hipMemcpyAsync(h_passes.data(), v.passes, (size_t)n * 4, hipMemcpyDeviceToHost, f.route));
+        if (int rc = play(f, v, side, d_counts, pooled ? &gm : nullptr, ss)) return rc;
+        // (slots mode: the last refill, before the route that found no root, stored the last results)
+        HIP_TRY(hipMemcpyAsync(h_progress.data(), pooled ? gm.progress : v.progress, (size_t)n, hipMemcpyDeviceToHost, f.route));
+        HIP_TRY(hipMemcpyAsync(h_plies.data(), pooled ? gm.plies : v.plies, (size_t)n * 4, hipMemcpyDeviceToHost, f.route));
+        HIP_TRY(hipMemcpyAsync(h_passes.data(), pooled ? gm.passes : v.passes, (size_t)n * 4, hipMemcpyDeviceToHost, f.route));
         return 0;
     };
     const int rc = run();
@@ -504,4 +614,21 @@ extern "C" int oaz_arena_fight(const oaz_arena_config* cfg, const oaz_arena_agen
         if (plies) plies[k] = h_plies[(size_t)k];
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int oaz_arena_fight(const oaz_arena_config* cfg, const oaz_arena_agent* agent, const oaz_arena_agent* opponent,
+                               double agent_rating, double opponent_rating, oaz_fight_stats* stats, uint8_t* results,
+                               int32_t* plies, double* history) {
+    return fight_on(cfg, 0, agent, opponent, agent_rating, opponent_rating, stats, results, plies, history, nullptr);
+}
+
+extern "C" int oaz_arena_fight_slots(const oaz_arena_config* cfg, int32_t slots, const oaz_arena_agent* agent,
+                                     const oaz_arena_agent* opponent, double agent_rating, double opponent_rating,
+                                     oaz_fight_stats* stats, uint8_t* results, int32_t* plies, double* history,
+                                     oaz_arena_slots_stats* slot_stats) {
+    if (int rc = check_arena_config(cfg)) return rc;  // (before the slot count, as the lock-step entry reports them)
+    if (slots < 1) return oaz_set_err(OAZ_ERR_ARG, "arena: slots %d", slots);
+    return fight_on(cfg, slots, agent, opponent, agent_rating, opponent_rating, stats, results, plies, history, slot_stats);
 }

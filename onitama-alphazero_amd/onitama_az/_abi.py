@@ -238,6 +238,16 @@ class oaz_fight_stats(C.Structure):
     ]
 
 
+class oaz_arena_slots_stats(C.Structure):
+    _fields_ = [
+        ("rounds", C.c_uint64),
+        ("searches", C.c_uint64 * 2),
+        ("max_batch", C.c_uint32 * 2),
+        ("slots", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class oaz_comm_id(C.Structure):
     _fields_ = [("internal", C.c_char * 128)]
 
@@ -261,6 +271,7 @@ assert C.sizeof(oaz_node) == 32
 assert C.sizeof(oaz_sample) == 228
 assert C.sizeof(oaz_config) == 120 and oaz_config.search_time_ns.offset == 104
 assert C.sizeof(oaz_arena_agent) == 88 and C.sizeof(oaz_arena_config) == 40 and C.sizeof(oaz_fight_stats) == 96
+assert C.sizeof(oaz_arena_slots_stats) == 40
 
 STATE_DTYPE = np.dtype(
     [("kings", "<u4", 2), ("pawns", "<u4", 2), ("cards", "u1", 5), ("to_move", "u1"), ("pad", "u1", 2)]
@@ -354,6 +365,10 @@ _PROTOS = {
     "oaz_arena_capacity": (C.c_int, [_P(oaz_arena_config), _P(C.c_int32 * 2)]),
     "oaz_arena_fight": (C.c_int, [_P(oaz_arena_config), _P(oaz_arena_agent), _P(oaz_arena_agent), C.c_double,
                                   C.c_double, _P(oaz_fight_stats), _VOIDP, _VOIDP, _VOIDP]),
+    "oaz_arena_slots_capacity": (C.c_int, [_P(oaz_arena_config), C.c_int32, _P(C.c_int32 * 2)]),
+    "oaz_arena_fight_slots": (C.c_int, [_P(oaz_arena_config), C.c_int32, _P(oaz_arena_agent), _P(oaz_arena_agent),
+                                        C.c_double, C.c_double, _P(oaz_fight_stats), _VOIDP, _VOIDP, _VOIDP,
+                                        _P(oaz_arena_slots_stats)]),
     "oaz_train_config_default": (None, [_P(oaz_train_config)]),
     "oaz_trainer_create": (_VOIDP, [_P(oaz_train_config), C.c_int]),
     "oaz_trainer_destroy": (None, [_VOIDP]),

@@ -3,7 +3,8 @@
 The game states stay on the GPU for the whole fight (routing, the Random agent and the move application are
 kernels of oaz_arena.hip; an AlphaZero side's engine searches the roots where the router left them), the
 host reads two counts per ply, and Elo is folded over the results in game order at the end, so the
-statistics equal `evaluator.fight`'s game for game for the same agents and seeds.
+statistics equal `evaluator.fight`'s game for game for the same agents and seeds. `native_fight(slots=S)` plays
+the same fight on a pool of S game slots that are refilled on the device as games end (oaz_arena_fight_slots).
 """
 from __future__ import annotations
 
@@ -64,6 +65,14 @@ def arena_capacity(cfg: _abi.oaz_arena_config):
     return int(out[0]), int(out[1])
 
 
+def arena_slots_capacity(cfg: _abi.oaz_arena_config, slots: int):
+    """Largest batch (agent, opponent) answer per round in a fight of cfg on `slots` slots
+    (oaz_arena_slots_capacity): arena_capacity's for slots >= game_amnt, else (slots, slots)."""
+    out = (C.c_int32 * 2)()
+    _abi.check(_abi.load().oaz_arena_slots_capacity(C.byref(cfg), int(slots), C.byref(out)))
+    return int(out[0]), int(out[1])
+
+
 def _device_of(agent) -> int:
     if isinstance(agent, AlphaZeroAgent):
         return int(agent.mcts.model.options.device)
@@ -95,17 +104,23 @@ def _describe(agent, need: int) -> _abi.oaz_arena_agent:
 
 
 def native_fight(config: EvaluatorConfig, agent, opponent, agent_rating: float = 800.0,
-                 opponent_rating: float = 800.0) -> FightStatistics:
+                 opponent_rating: float = 800.0, slots=None) -> FightStatistics:
     """evaluator.rs:355-399 as one oaz_arena_fight call. The agents are the objects `evaluator.fight` takes
     (AlphaZeroAgent, Mcts, AlphaBeta) or a NativeRandomAgent; an AlphaZeroAgent's shared search engine is
     sized for the batch the fight needs and searched with the agent's config. A pure-MCTS side's c-th search of
     the fight draws from the streams `evaluator.fight` gives a fresh Mcts object's c-th call (c << 20). The
-    returned statistics also carry `passes` and `plies_total` (oaz_fight_stats)."""
+    returned statistics also carry `passes` and `plies_total` (oaz_fight_stats).
+
+    slots=S plays the fight on min(S, game_amnt) game slots through oaz_arena_fight_slots (`evaluator.fight_slots`
+    is its host-loop statement): a finished slot is dealt the fight's next game on the device, the engines are
+    sized for S slots instead of game_amnt games, and the statistics equal the lock-step fight's game for game
+    for every agent but a pure-MCTS one, whose streams follow the slots (include/onitama_az.h). They then also
+    carry `rounds`, `searches`, `max_batch` and `slots` (oaz_arena_slots_stats). slots=None is the lock-step call."""
     devs = {d for d in (_device_of(agent), _device_of(opponent)) if d >= 0}
     if len(devs) > 1:
         raise ValueError(f"native_fight: the agents are on different devices {sorted(devs)}")
     cfg = arena_config(config, devs.pop() if devs else 0)
-    need = arena_capacity(cfg)
+    need = arena_capacity(cfg) if slots is None else arena_slots_capacity(cfg, slots)
     # (an engine shared by both sides is made once, for the larger need: both needs are equal)
     sides = [_describe(agent, need[0]), _describe(opponent, need[1])]
     if sides[0].kind == sides[1].kind == _abi.AGENT_ALPHAZERO and agent.mcts.model is opponent.mcts.model:
@@ -118,9 +133,15 @@ def native_fight(config: EvaluatorConfig, agent, opponent, agent_rating: float =
     results = np.zeros(n, dtype=np.uint8)
     plies = np.zeros(n, dtype=np.int32)
     history = np.zeros((n, 4), dtype=np.float64)
-    _abi.check(_abi.load().oaz_arena_fight(C.byref(cfg), C.byref(sides[0]), C.byref(sides[1]), float(agent_rating),
-                                           float(opponent_rating), C.byref(st), _abi.ptr(results), _abi.ptr(plies),
-                                           _abi.ptr(history)))
+    if slots is None:
+        _abi.check(_abi.load().oaz_arena_fight(C.byref(cfg), C.byref(sides[0]), C.byref(sides[1]), float(agent_rating),
+                                               float(opponent_rating), C.byref(st), _abi.ptr(results), _abi.ptr(plies),
+                                               _abi.ptr(history)))
+    else:
+        ss = _abi.oaz_arena_slots_stats()
+        _abi.check(_abi.load().oaz_arena_fight_slots(C.byref(cfg), int(slots), C.byref(sides[0]), C.byref(sides[1]),
+                                                     float(agent_rating), float(opponent_rating), C.byref(st),
+                                                     _abi.ptr(results), _abi.ptr(plies), _abi.ptr(history), C.byref(ss)))
     out = FightStatistics(st.rating_a, st.rating_b)
     out.general = WinLoseDraws(st.wins, st.loses, st.draws)
     out.color = [WinLoseDraws(st.color_wins[c], st.color_loses[c], st.color_draws[c]) for c in (0, 1)]
@@ -130,4 +151,7 @@ def native_fight(config: EvaluatorConfig, agent, opponent, agent_rating: float =
     out.plies = [int(p) for p in plies]
     out.passes = int(st.passes)
     out.plies_total = int(st.plies_total)
+    if slots is not None:
+        out.rounds, out.slots = int(ss.rounds), int(ss.slots)
+        out.searches, out.max_batch = [int(x) for x in ss.searches], [int(x) for x in ss.max_batch]
     return out

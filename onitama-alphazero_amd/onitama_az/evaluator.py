@@ -243,13 +243,81 @@ def fight(config: EvaluatorConfig, agent: BatchedAgent, opponent: BatchedAgent, 
     return stats
 
 
+def fight_slots(config: EvaluatorConfig, agent: BatchedAgent, opponent: BatchedAgent, agent_rating: float = 800.0,
+                opponent_rating: float = 800.0, slots: int = 1) -> FightStatistics:
+    """`fight` on S = min(slots, game_amnt) game slots: the host-loop statement of oaz_arena_fight_slots's schedule
+    (include/onitama_az.h). Slot i starts game i; before every round each slot that finished stores its result
+    under its game index and the finished slots take the fight's next games in ascending slot order; a round
+    lets each side answer its active slots, in ascending slot order, in one batch; the fight ends when no slot
+    is active. begin_turn gets the slots' game indices and plies. The returned statistics also carry `rounds`."""
+    n = config.game_amnt
+    if slots < 1:
+        raise ValueError(f"fight_slots: slots {slots}")
+    S = min(int(slots), n)
+    decks = [config.deck.indices() if config.deck is not None else list(Deck.default(config.seed, k).indices())
+             for k in range(n)]
+    starts = np.concatenate([initial_state_np(d) for d in decks]) if n else np.zeros(0, _abi.STATE_DTYPE)
+    states = starts[:S].copy()
+    game = np.arange(S, dtype=np.int64)  # the game a slot holds; -1: none
+    progress = np.full(S, _abi.IN_PROGRESS, dtype=np.uint8)
+    active = np.ones(S, dtype=bool)
+    budget = np.full(S, config.max_plies, dtype=np.int64)
+    plies = np.zeros(S, dtype=np.int64)
+    game_progress = np.full(n, _abi.IN_PROGRESS, dtype=np.uint8)
+    game_plies = np.zeros(n, dtype=np.int64)
+    nxt, rounds = S, 0
+    agent.reserve(S)
+    opponent.reserve(S)
+    ka, kb = (getattr(a, "device_key", lambda: None)() for a in (agent, opponent))
+    concurrent = ka is not None and kb is not None and ka != kb  # (as in fight)
+    with ThreadPoolExecutor(max_workers=2 if concurrent else 1) as pool:
+        while True:
+            for i in np.where(~active & (game >= 0))[0]:  # harvest, then refill in ascending slot order
+                game_progress[game[i]], game_plies[game[i]] = progress[i], plies[i]
+                if nxt < n:
+                    states[i], game[i], nxt = starts[nxt], nxt, nxt + 1
+                    progress[i], active[i], budget[i], plies[i] = _abi.IN_PROGRESS, True, config.max_plies, 0
+                else:
+                    game[i] = -1
+            if not active.any():
+                break
+            rounds += 1
+            red_to_move = states["to_move"] == 0
+            agent_moves = active & (red_to_move == (game % 2 == 0))
+            turns = [(np.where(who)[0], ag) for who, ag in ((agent_moves, agent), (active & ~agent_moves, opponent))]
+            turns = [(idx, ag) for idx, ag in turns if len(idx)]
+            for idx, ag in turns:
+                if hasattr(ag, "begin_turn"):
+                    ag.begin_turn(game[idx], plies[idx])
+            if concurrent and len(turns) == 2:
+                futs = [pool.submit(ag.generate_moves_np, np.ascontiguousarray(states[idx])) for idx, ag in turns]
+                moves = [f.result() for f in futs]
+            else:
+                moves = [ag.generate_moves_np(np.ascontiguousarray(states[idx])) for idx, ag in turns]
+            for (idx, _), mv in zip(turns, moves):
+                progress[idx] = _apply(states, idx, mv)
+            plies[active] += 1
+            won = (progress == _abi.RED_WIN) | (progress == _abi.BLUE_WIN)
+            cut = active & ~won & (budget < 0)
+            budget[active] -= 1
+            active &= ~won & ~cut
+    stats = FightStatistics(agent_rating, opponent_rating)
+    for k in range(n):  # Elo in game order
+        stats.update(MoveResult(int(game_progress[k])), PlayerColor.Red if k % 2 == 0 else PlayerColor.Blue)
+        stats.results.append(int(game_progress[k]))
+        stats.plies.append(int(game_plies[k]))
+    stats.rounds = rounds
+    return stats
+
+
 class Evaluator:  # evaluator.rs:139-193
     def __init__(self, config: EvaluatorConfig, best: ConvResNet, new: ConvResNet,
                  ratings: Sequence[Tuple[float, float]] = ((800.0, 800.0), (800.0, 800.0), (800.0, 800.0))):
         self.config, self.best, self.new, self.ratings = config, best, new, ratings
 
     def pit(self, sims: int = 400, concurrent: bool = True, alphabeta: bool = False,
-            enforce_search_time: bool = True, native: bool = False) -> Tuple[PitStatistics, bool]:
+            enforce_search_time: bool = True, native: bool = False,
+            slots: Optional[int] = None) -> Tuple[PitStatistics, bool]:
         """evaluator.rs:169-193. The reference starts the fights on threads of their own, each with
         its own copy of the networks (`VarStore::copy`, evaluator.rs:206-231); here each fight gets
         weight copies too, so every fight searches on engines of its own and the fights run at the
@@ -268,11 +336,21 @@ class Evaluator:  # evaluator.rs:139-193
         native=True plays every fight on the device through oaz_arena_fight (arena.native_fight), on the same
         threads and weight copies; the random opponent is then arena.NativeRandomAgent(config.seed), whose draws
         are keyed by (game, ply) instead of numpy's stream, so the random fight's games differ from the
-        default's while the other fights' are the same."""
+        default's while the other fights' are the same.
+
+        slots=S (native=True only, else ValueError) plays every fight on min(S, game_amnt) refilled game slots
+        (arena.native_fight(slots=S), oaz_arena_fight_slots): the engines then hold S trees each instead of
+        game_amnt (8.4 GB instead of 134 GB for the four at 4 096 slots x 400 sims, plus 33 B per game), and the
+        self, random and alpha-beta fights' statistics are the same; the pure-MCTS fight's streams follow the slots,
+        so it equals `fight_slots`."""
+        if slots is not None and not native:
+            raise ValueError("pit: slots needs native=True")
         play, random_agent = fight, RandomAgent
         if native:
+            import functools
+
             from .arena import NativeRandomAgent, native_fight
-            play, random_agent = native_fight, NativeRandomAgent
+            play, random_agent = functools.partial(native_fight, slots=slots), NativeRandomAgent
         cfg = AlphaZeroMctsConfig(search_time=0.4, max_playouts=sims, train=False,  # evaluator.rs:198-204
                                   enforce_search_time=enforce_search_time)
         from .pure_mcts import Mcts  # evaluator.rs:314-353: Mcts{400 ms, min visits 5, c 1.41, 400 playouts}

@@ -76,7 +76,8 @@ def default_agents(model, seed: int = 20260101, device: int = 0) -> dict:
 
 class Tournament:
     """bin/tournament.rs `pit`. The agents are what `evaluator.fight` takes (generate_moves_np, name, reserve);
-    see default_agents for the reference's four. `play` is the fight (evaluator.fight by default)."""
+    see default_agents for the reference's four. `play` is the fight (evaluator.fight by default); `play=functools.partial(arena.native_fight, slots=S)`
+    plays every pairing on a pool of S refilled game slots, with the AlphaZero engine sized for S."""
 
     def __init__(self, alphabeta, mcts, alphazero, random, game_amnt: int = 100, max_plies: int = 150,
                  seed: int = 20260101, play: Optional[Callable] = None, verbose: bool = True):

@@ -19,8 +19,20 @@ Per-ply host time outside the searches:
           sides are both the Random agent: routing, one trivial kernel per side, the move application and the
           8-byte read-back per ply, over that fight's plies.
 
+A case written games@slots (az_vs_az:65536@4096, az_vs_random:65536@4096) measures the pool of refilled game
+slots (oaz_arena_fight_slots) instead, three alternatives alternating in the same way:
+  (a) native_fight(slots=S) of `games` games on engines of S games;
+  (b) the lock-step native_fight of `games` games on engines of `games` games;
+  (c) games / S consecutive lock-step native_fights of S games (deal seeds seed, seed + 1, ...) on (a)'s engines:
+      what (a)'s memory could do before.
+(a) and (b) must return the same per-game results, which the tool checks. Reported per alternative: games/s, rounds
+(a lock-step fight's are its longest game), the mean batch a round searched (moves made / rounds), and the two
+engines' tree bytes from their shapes (games x (1 + 40 x sims) nodes of 32 B); for (a) also the mean batch per
+search and the per-round time of a Random-vs-Random fight on the same pool (no searches).
+
 usage: python tools/arena_bench.py [--out profiles/arena_native_<date>.json] [--reps 5] [--sims 400]
-                                   [--cases az_vs_az:4096,az_vs_random:4096,az_vs_random:65536,az_vs_alphabeta:4096]"""
+                                   [--cases az_vs_az:4096,az_vs_random:4096,az_vs_random:65536,az_vs_alphabeta:4096]
+       python tools/arena_bench.py --out profiles/arena_slots_<date>.json --cases az_vs_az:65536@4096,az_vs_random:65536@4096"""
 from __future__ import annotations
 
 import argparse
@@ -142,6 +154,72 @@ def run_case(kind: str, games: int, sims: int, reps: int, nets) -> dict:
     return row
 
 
+def run_slots_case(kind: str, games: int, slots: int, sims: int, reps: int, weights) -> dict:
+    cfg = EvaluatorConfig(game_amnt=games, max_plies=150, seed=3)
+    mcfg = AlphaZeroMctsConfig(max_playouts=sims, train=False, enforce_search_time=False)
+    # two sets of networks, so that (b)'s engines of `games` games are not the ones (a) and (c) run on
+    small, big = [[ConvResNet(ConvResNetConfig(resnet_block_amnt=3), weights=np.array(w, copy=True)) for w in weights]
+                  for _ in range(2)]
+
+    def sides(nets):
+        agent = AlphaZeroAgent(mcfg, nets[0])
+        if kind == "az_vs_az":
+            return agent, AlphaZeroAgent(mcfg, nets[1])
+        if kind == "az_vs_random":
+            return agent, NativeRandomAgent(cfg.seed)
+        raise SystemExit(f"unknown slots case {kind}")
+
+    def timed(f):
+        t0 = time.perf_counter()
+        st = f()
+        return st, time.perf_counter() - t0
+
+    def pool():
+        return native_fight(cfg, *sides(small), slots=slots)
+
+    def lock_step():
+        return native_fight(cfg, *sides(big))
+
+    def chunks():
+        return [native_fight(EvaluatorConfig(game_amnt=slots, max_plies=150, seed=cfg.seed + i), *sides(small))
+                for i in range(games // slots)]
+
+    runs = {"a": pool, "b": lock_step, "c": chunks}
+    last = {k: f() for k, f in runs.items()}  # warm-up of each: engines, kernels
+    ts = {k: [] for k in runs}
+    for _ in range(reps):  # alternating, same process
+        for k, f in runs.items():
+            last[k], dt = timed(f)
+            ts[k].append(dt)
+        print(f"# {kind} {games}@{slots}: " + ", ".join(f"({k}) {ts[k][-1]:.3f} s" for k in runs), flush=True)
+    a, b, c = last["a"], last["b"], last["c"]
+    rr = [NativeRandomAgent(1), NativeRandomAgent(2)]
+    native_fight(cfg, *rr, slots=slots)
+    rr_st, rr_dt = timed(lambda: native_fight(cfg, *rr, slots=slots))
+    engines = 2 if kind == "az_vs_az" else 1
+    tree = lambda g: engines * g * (1 + 40 * sims) * 32  # noqa: E731
+
+    def row(t, rounds, moves, g):
+        return {**spread(t), "games_per_s": games / statistics.median(t), "rounds": rounds,
+                "mean_batch_per_round": moves / rounds, "engine_tree_bytes": tree(g)}
+
+    out = {"case": kind, "games": games, "slots": slots, "sims": sims, "reps": reps,
+           "a_slots": {**row(ts["a"], a.rounds, a.plies_total, slots),
+                       "mean_batch_per_search": a.plies_total / (a.searches[0] + a.searches[1]),
+                       "searches": a.searches, "max_batch": a.max_batch, "extra_bytes_per_game": 33,
+                       "per_round_without_searches_ms": 1e3 * rr_dt / rr_st.rounds,
+                       "random_vs_random_fight_s": rr_dt, "random_vs_random_rounds": rr_st.rounds},
+           "b_lock_step": row(ts["b"], max(b.plies), b.plies_total, games),
+           "c_chunks": row(ts["c"], sum(max(f.plies) for f in c), sum(f.plies_total for f in c), slots),
+           "same_games_a_b": bool(a.results == b.results and a.plies == b.plies),
+           "a_slowest_over_c_fastest_time": max(ts["a"]) / min(ts["c"]),
+           "a_beats_c_beyond_spread": bool(max(ts["a"]) < min(ts["c"])),
+           "a_over_b_time": statistics.median(ts["a"]) / statistics.median(ts["b"])}
+    if not out["same_games_a_b"]:
+        raise SystemExit(f"{kind} {games}@{slots}: the pool's games differ from the lock-step fight's")
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=str(ROOT / "profiles" / f"arena_native_{datetime.date.today():%Y%m%d}.json"))
@@ -166,8 +244,13 @@ def main() -> int:
             out["cases"] = old.get("cases", [])
     for spec in args.cases.split(","):
         kind, games = spec.split(":")
-        row = run_case(kind, int(games), args.sims, args.reps, nets)
-        out["cases"] = [c for c in out["cases"] if (c["case"], c["games"]) != (kind, int(games))] + [row]
+        games, _, slots = games.partition("@")
+        if slots:
+            row = run_slots_case(kind, int(games), int(slots), args.sims, args.reps, [n.weights for n in nets])
+        else:
+            row = run_case(kind, int(games), args.sims, args.reps, nets)
+        out["cases"] = [c for c in out["cases"]
+                        if (c["case"], c["games"], c.get("slots")) != (kind, int(games), row.get("slots"))] + [row]
         print(json.dumps(row), flush=True)
         path.write_text(json.dumps(out, indent=1) + "\n")
     print("wrote", args.out)
