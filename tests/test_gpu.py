@@ -278,7 +278,7 @@ def test_nn_bf16_mode_close_to_fp32_goldens(nn_golden, trained3, name, blocks):
     assert np.allclose(p.reshape(-1, 50).sum(1), 1.0, atol=1e-5)
 
 
-@pytest.mark.parametrize("precision", [_abi.FP32, _abi.FP32_SPLIT16])
+@pytest.mark.parametrize("precision", [_abi.FP32, _abi.FP32_SPLIT16, _abi.FP32_SPLIT, _abi.BF16])
 def test_nn_batch_position_invariance(orc, precision):
     pos = random_positions(orc, 64, seed=404)
     with Engine(games=1024, sims=1, blocks=3, precision=precision) as e:
@@ -344,7 +344,7 @@ def test_search_uneven_parts_compacted_trees_bitexact(orc, games, parts):
 
 
 @pytest.mark.parametrize("compact,parts", [(0, 1), (1, 2)])
-@pytest.mark.parametrize("precision", [_abi.FP32, _abi.FP32_SPLIT16])
+@pytest.mark.parametrize("precision", [_abi.FP32, _abi.FP32_SPLIT16, _abi.FP32_SPLIT, _abi.BF16])
 def test_search_nn_trees_bitexact_with_gpu_evaluator(orc, precision, compact, parts):
     """Real network: the oracle's search is fed the GPU network's outputs (batch-1 calls of
     the same kernel), so both searches see identical evaluations and must agree exactly."""
