@@ -24,6 +24,7 @@
 #include "oaz_host.h"
 #include "oaz_kernels.h"
 #include "oaz_pack.h"
+#include "oaz_weights_layout.h"
 
 using namespace oaz;
 
@@ -94,50 +95,26 @@ extern "C" size_t oaz_nn_device_bytes(int blocks, int precision) {
 }
 
 extern "C" size_t oaz_weight_count(int blocks, int channels, int in_planes) {
-    const size_t C = (size_t)channels, I = (size_t)in_planes;
-    size_t n = C * I * 9 + C + 4 * C;
-    n += (size_t)blocks * 2 * (C * C * 9 + C + 4 * C);
-    n += C + 1 + 4 + C * 25 + C + C + 1;
-    n += 2 * C + 2 + 8 + 50 * 50 + 50;
-    return n;
+    return wl::layout(blocks, (size_t)channels, (size_t)in_planes).total;
 }
 
+// Weights and biases U(+-1/sqrt(fan_in)), one draw per element in blob order; BN gamma 1, beta 0, mean 0, var 1.
 extern "C" int oaz_random_weights(uint64_t seed, int blocks, float* out, size_t n) {
-    const size_t need = oaz_weight_count(blocks, 64, 21);
-    if (!out || n != need || blocks < 0) return oaz_set_err(OAZ_ERR_ARG, "random_weights: need %zu floats", need);
+    const wl::Layout L = wl::layout(blocks);
+    if (!out || n != L.total || blocks < 0) return oaz_set_err(OAZ_ERR_ARG, "random_weights: need %zu floats", L.total);
     uint64_t ctr = 0;
-    auto uni = [&](float bound) {
-        const uint64_t r = splitmix64(seed ^ splitmix64(ctr++));
-        const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0);
-        return (float)((2.0 * u - 1.0) * bound);
-    };
-    float* p = out;
-    auto conv = [&](size_t wn, int cout, size_t fan_in) {  // weight + bias U(+-1/sqrt(fan_in))
-        const float b = (float)(1.0 / sqrt((double)fan_in));
-        for (size_t i = 0; i < wn; ++i) *p++ = uni(b);
-        for (int i = 0; i < cout; ++i) *p++ = uni(b);
-    };
-    auto bn = [&](int c) {  // gamma 1, beta 0, mean 0, var 1
-        for (int i = 0; i < c; ++i) *p++ = 1.0f;
-        for (int i = 0; i < c; ++i) *p++ = 0.0f;
-        for (int i = 0; i < c; ++i) *p++ = 0.0f;
-        for (int i = 0; i < c; ++i) *p++ = 1.0f;
-    };
-    conv(64 * 21 * 9, 64, 21 * 9);
-    bn(64);
-    for (int b = 0; b < blocks; ++b)
-        for (int j = 0; j < 2; ++j) {
-            conv(64 * 64 * 9, 64, 64 * 9);
-            bn(64);
+    for (const wl::Tensor& t : L.tensors) {
+        const float bound = t.fan_in ? (float)(1.0 / sqrt((double)t.fan_in)) : 0.0f;
+        for (size_t i = 0; i < t.numel; ++i) {
+            if (!t.fan_in) {
+                out[t.offset + i] = t.fill;
+                continue;
+            }
+            const uint64_t r = splitmix64(seed ^ splitmix64(ctr++));
+            const double u = (double)(r >> 11) * (1.0 / 9007199254740992.0);
+            out[t.offset + i] = (float)((2.0 * u - 1.0) * bound);
         }
-    conv(64, 1, 64);
-    bn(1);
-    conv(64 * 25, 64, 25);
-    conv(64, 1, 64);
-    conv(128, 2, 64);
-    bn(2);
-    conv(2500, 50, 50);
-    if ((size_t)(p - out) != need) return oaz_set_err(OAZ_ERR_STATE, "random_weights: layout mismatch");
+    }
     return 0;
 }
 

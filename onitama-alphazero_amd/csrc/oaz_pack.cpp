@@ -1,9 +1,6 @@
 // oaz_pack.cpp — weights: canonical (tch VarStore order) -> BN-folded -> MFMA-packed, written at the
-// offsets of oaz_nn_layout.h into a zero-initialised image (so every pad is zero).
-// Canonical order (DESIGN.md "Weights"): conv_init_1.{weight,bias}, bn1.{weight,bias,
-// running_mean,running_var}, for each block i, j in {1,2}: resnet_i.resnet_small_block{j}.
-// {small_block_conv.{weight,bias}, small_block_bn.{4}}, vh_conv.{w,b}, vh_bn.{4},
-// vh_linear1.{w,b}, vh_linear2.{w,b}, policy_conv.{w,b}, policy_bn.{4}, ph_linear2.{w,b}.
+// offsets of oaz_nn_layout.h into a zero-initialised image (so every pad is zero). The canonical
+// blob is read at the offsets of oaz_weights_layout.h.
 #include "oaz_pack.h"
 
 #include <assert.h>
@@ -14,6 +11,7 @@
 #include <cmath>
 
 #include "oaz_nn_layout.h"
+#include "oaz_weights_layout.h"
 
 using namespace oaz;
 
@@ -24,22 +22,16 @@ struct FoldedConv {
     std::vector<float> b;  // [cout]
 };
 
-constexpr size_t raw_conv_bn(size_t cout, size_t cin, size_t taps) { return cout * cin * taps + cout + 4 * cout; }
-
-FoldedConv fold(const float*& p, int cout, int cin, int taps) {
+FoldedConv fold(const float* raw, const wl::ConvBn& c) {
     FoldedConv f;
-    const float* w = p;
-    p += (size_t)cout * cin * taps;
-    const float* b = p;
-    p += cout;
-    const float *g = p, *beta = p + cout, *mean = p + 2 * cout, *var = p + 3 * cout;
-    p += 4 * cout;
-    f.w.resize((size_t)cout * cin * taps);
-    f.b.resize(cout);
-    for (int o = 0; o < cout; ++o) {
+    const float *w = raw + c.w, *b = raw + c.b, *g = raw + c.gamma, *beta = raw + c.beta, *mean = raw + c.mean,
+                *var = raw + c.var;
+    const size_t per = c.cin * c.k * c.k;  // weights per output channel
+    f.w.resize(c.cout * per);
+    f.b.resize(c.cout);
+    for (size_t o = 0; o < c.cout; ++o) {
         const double s = (double)g[o] / sqrt((double)var[o] + 1e-5);  // BN eval, eps 1e-5
-        for (size_t k = 0; k < (size_t)cin * taps; ++k)
-            f.w[(size_t)o * cin * taps + k] = (float)((double)w[(size_t)o * cin * taps + k] * s);
+        for (size_t k = 0; k < per; ++k) f.w[o * per + k] = (float)((double)w[o * per + k] * s);
         f.b[o] = (float)(((double)b[o] - (double)mean[o]) * s + (double)beta[o]);
     }
     return f;
@@ -246,57 +238,48 @@ void pack_first_layer_f16(const FoldedConv& f, const std::vector<float>& T, floa
 }
 
 // The blob of one precision at out[0, nn_packed_floats) (zero on entry).
-void pack_blob(const float* raw, int blocks, int prec, float* out) {
-    const float* p = raw;
-    const FoldedConv f1 = fold(p, 64, 21, 9);
+void pack_blob(const float* raw, const wl::Layout& L, int prec, float* out) {
+    const int blocks = L.blocks;
+    const FoldedConv f1 = fold(raw, L.tower[0]);
     const std::vector<float> T = first_layer_table(f1);
     pack_first_layer(f1, T, out);
     for (int c = 0; c < 2 * blocks; ++c) {
         float* o = out + nnl::kConvs + (size_t)c * nnl::conv_stride(prec);
-        if (prec == OAZ_FP32) pack_conv64_f32(fold(p, 64, 64, 9), o);
-        else pack_conv64_x32(fold(p, 64, 64, 9), prec, o);
+        if (prec == OAZ_FP32) pack_conv64_f32(fold(raw, L.tower[1 + c]), o);
+        else pack_conv64_x32(fold(raw, L.tower[1 + c]), prec, o);
     }
     float* h = out + nnl::heads(prec, blocks);
     // value head: vh_conv + vh_bn folded, vh_linear1, vh_linear2
-    const FoldedConv vc = fold(p, 1, 64, 1);
+    const FoldedConv vc = fold(raw, L.vh_conv);
+    const float *l1w = raw + L.vh_linear1.w, *plw = raw + L.ph_linear2.w;
     memcpy(h + nnl::kWv, vc.w.data(), 64 * sizeof(float));
     h[nnl::kBv] = vc.b[0];
     for (int q = 0; q < 25; ++q)  // vh_linear1.weight [64][25], stored transposed [25][64] (coalesced per lane)
-        for (int o = 0; o < 64; ++o) h[nnl::kL1w + q * 64 + o] = p[o * 25 + q];
-    p += 64 * 25;
-    memcpy(h + nnl::kL1b, p, 64 * sizeof(float));  // vh_linear1.bias
-    memcpy(h + nnl::kL2w, p + 64, 64 * sizeof(float));  // vh_linear2.weight [1][64]
-    h[nnl::kL2b] = p[128];                              // vh_linear2.bias
-    p += 129;
+        for (int o = 0; o < 64; ++o) h[nnl::kL1w + q * 64 + o] = l1w[o * 25 + q];
+    memcpy(h + nnl::kL1b, raw + L.vh_linear1.b, 64 * sizeof(float));  // vh_linear1.bias
+    memcpy(h + nnl::kL2w, raw + L.vh_linear2.w, 64 * sizeof(float));  // vh_linear2.weight [1][64]
+    h[nnl::kL2b] = raw[L.vh_linear2.b];                               // vh_linear2.bias
     // policy head: policy_conv + policy_bn folded, ph_linear2
-    const FoldedConv pc = fold(p, 2, 64, 1);
+    const FoldedConv pc = fold(raw, L.policy_conv);
     memcpy(h + nnl::kWp, pc.w.data(), 128 * sizeof(float));
     h[nnl::kBp] = pc.b[0];
     h[nnl::kBp + 1] = pc.b[1];
     for (int f = 0; f < 50; ++f)  // ph_linear2.weight [50 out][50 in], stored transposed [in][out]
-        for (int o = 0; o < 50; ++o) h[nnl::kPlw + f * 50 + o] = p[o * 50 + f];
-    p += 2500;
-    memcpy(h + nnl::kPlb, p, 50 * sizeof(float));  // ph_linear2.bias
-    p += 50;
+        for (int o = 0; o < 50; ++o) h[nnl::kPlw + f * 50 + o] = plw[o * 50 + f];
+    memcpy(h + nnl::kPlb, raw + L.ph_linear2.b, 50 * sizeof(float));  // ph_linear2.bias
     if (prec != OAZ_FP32) pack_head_frags(vc, pc, prec, h);
     if (nnl::has_l1c(prec)) pack_first_layer_f16(f1, T, out + nnl::l1c(prec, blocks));
-    assert((size_t)(p - raw) == oaz_pack_raw_floats(blocks));
 }
 
 }  // namespace
 
-size_t oaz_pack_raw_floats(int blocks) {
-    return raw_conv_bn(64, 21, 9) + (size_t)blocks * 2 * raw_conv_bn(64, 64, 9) +  // the tower
-           raw_conv_bn(1, 64, 1) + (64 * 25 + 64) + (64 + 1) +                     // value head
-           raw_conv_bn(2, 64, 1) + (50 * 50 + 50);                                 // policy head
-}
-
 int oaz_pack_weights(const float* raw, size_t raw_floats, int blocks, int precision, std::vector<float>& out) {
     if (!raw || blocks < 0 || precision < OAZ_FP32 || precision > OAZ_FP32_SPLIT16) return OAZ_PACK_BAD_ARG;
-    if (raw_floats != oaz_pack_raw_floats(blocks)) return OAZ_PACK_RAW_SIZE;
+    const wl::Layout L = wl::layout(blocks);
+    if (raw_floats != L.total) return OAZ_PACK_RAW_SIZE;
     out.assign(nn_device_floats(blocks, precision), 0.0f);
-    pack_blob(raw, blocks, precision, out.data());
+    pack_blob(raw, L, precision, out.data());
     // k_nn_h3 recomputes fp16-range tiles with the k_nn_x6 body: the OAZ_FP32_SPLIT blob follows
-    if (precision == OAZ_FP32_SPLIT16) pack_blob(raw, blocks, OAZ_FP32_SPLIT, out.data() + nn_packed_floats(blocks, precision));
+    if (precision == OAZ_FP32_SPLIT16) pack_blob(raw, L, OAZ_FP32_SPLIT, out.data() + nn_packed_floats(blocks, precision));
     return OAZ_PACK_OK;
 }

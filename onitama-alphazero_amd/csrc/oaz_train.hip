@@ -29,13 +29,13 @@
 #include "../../include/onitama_az.h"
 #include "oaz_device.h"
 #include "oaz_host.h"
+#include "oaz_weights_layout.h"
 
 using namespace oaz;
 
 namespace tr {
 
 constexpr int kC = 64;       // hidden channels
-constexpr int kIn = 21;      // input planes
 constexpr int kInPad = 32;   // padded input row stride
 constexpr int kMaxConv = 1 + 2 * 16;
 constexpr int kHeadW = 64 * 25 + 64 + 64 + 1 + 2500 + 50;  // value MLP + policy linear grads
@@ -964,46 +964,15 @@ __global__ void k_pack(const float* W, int cin, int chunks, float4* wf, float4* 
 using namespace tr;
 
 // ---- host trainer ---------------------------------------------------------------------------------
-struct Layout {
-    size_t cw[kMaxConv], cb[kMaxConv], bg[kMaxConv], bb[kMaxConv], brm[kMaxConv], brv[kMaxConv];
-    HeadOff h;
-    size_t total;
-};
-
-static Layout make_layout(int blocks) {  // weights.py canonical_layout / VarStore order
-    Layout L{};
-    size_t p = 0;
-    const int nconv = 1 + 2 * blocks;
-    for (int l = 0; l < nconv; ++l) {
-        const size_t cin = l == 0 ? kIn : kC;
-        L.cw[l] = p; p += kC * cin * 9;
-        L.cb[l] = p; p += kC;
-        L.bg[l] = p; p += kC;
-        L.bb[l] = p; p += kC;
-        L.brm[l] = p; p += kC;
-        L.brv[l] = p; p += kC;
-    }
-    HeadOff& h = L.h;
-    h.vcw = (int)p; p += 64;
-    h.vcb = (int)p; p += 1;
-    h.vg = (int)p; p += 1;
-    h.vb = (int)p; p += 1;
-    h.vrm = (int)p; p += 1;
-    h.vrv = (int)p; p += 1;
-    h.l1w = (int)p; p += 64 * 25;
-    h.l1b = (int)p; p += 64;
-    h.l2w = (int)p; p += 64;
-    h.l2b = (int)p; p += 1;
-    h.pcw = (int)p; p += 128;
-    h.pcb = (int)p; p += 2;
-    h.pg = (int)p; p += 2;
-    h.pb = (int)p; p += 2;
-    h.prm = (int)p; p += 2;
-    h.prv = (int)p; p += 2;
-    h.plw = (int)p; p += 2500;
-    h.plb = (int)p; p += 50;
-    L.total = p;
-    return L;
+static HeadOff head_off(const wl::Layout& L) {
+    const wl::ConvBn &v = L.vh_conv, &p = L.policy_conv;
+    const wl::Linear &l1 = L.vh_linear1, &l2 = L.vh_linear2, &pl = L.ph_linear2;
+    HeadOff h{};
+    h.vcw = (int)v.w, h.vcb = (int)v.b, h.vg = (int)v.gamma, h.vb = (int)v.beta, h.vrm = (int)v.mean, h.vrv = (int)v.var;
+    h.l1w = (int)l1.w, h.l1b = (int)l1.b, h.l2w = (int)l2.w, h.l2b = (int)l2.b;
+    h.pcw = (int)p.w, h.pcb = (int)p.b, h.pg = (int)p.gamma, h.pb = (int)p.beta, h.prm = (int)p.mean, h.prv = (int)p.var;
+    h.plw = (int)pl.w, h.plb = (int)pl.b;
+    return h;
 }
 
 // The device resources are owning members (oaz_host.h), destroyed in reverse declaration order after
@@ -1015,7 +984,8 @@ struct oaz_trainer {
     Stream own;                // the trainer's stream
     hipStream_t st = nullptr;  // the stream its work runs on: own, or the caller's (oaz_trainer_set_stream)
     Stream st2;                // weight-gradient stream: wgrad(l) overlaps dgrad(l) on st
-    Layout L{};
+    wl::Layout L;  // the canonical blob (oaz_weights_layout.h): P, G and MOM are laid out by it
+    HeadOff h{};   // its head offsets, as the kernels take them
     int nconv = 0, maxB = 0;
     int cfin = -1;     // forward BN finalisation in k_bn_act_cfin (-1: one float4 per thread; A/B build: 0 = the
                        // separate k_bn_fwd_fin + k_bn_act launches, n > 0 = n workgroups)
@@ -1099,11 +1069,7 @@ static int trainer_init(oaz_trainer* t) {
         t->alloc(t->hcpart, ((R + 63) / 64) * (size_t)kHConvW) || t->alloc(t->pi, (size_t)t->maxB * 50) ||
         t->alloc(t->z, (size_t)t->maxB) || t->alloc(t->loss_acc, 4) || t->alloc(t->cur, 1))
         return OAZ_ERR_HIP;
-    std::vector<uint8_t> mask(t->nparam, 1);
-    for (int l = 0; l < t->nconv; ++l)
-        for (int c = 0; c < 64; ++c) mask[t->L.brm[l] + c] = mask[t->L.brv[l] + c] = 0;
-    mask[t->L.h.vrm] = mask[t->L.h.vrv] = 0;
-    mask[t->L.h.prm] = mask[t->L.h.prm + 1] = mask[t->L.h.prv] = mask[t->L.h.prv + 1] = 0;
+    const std::vector<uint8_t> mask = wl::sgd_mask(t->L);  // no SGD, no weight decay on the running statistics
     HIP_TRY(hipMemcpyAsync(t->mask, mask.data(), t->nparam, hipMemcpyHostToDevice, t->own));
     HIP_TRY(hipStreamSynchronize(t->own));  // the zero fills and the mask landed before any step
     return 0;
@@ -1126,7 +1092,8 @@ extern "C" oaz_trainer* oaz_trainer_create(const oaz_train_config* cfg, int devi
     t->device = device;
     t->nconv = 1 + 2 * cfg->blocks;
     t->maxB = cfg->max_batch;
-    t->L = make_layout(cfg->blocks);
+    t->L = wl::layout(cfg->blocks);
+    t->h = head_off(t->L);
 #if OAZ_AB  // A/B build only: conv row-group override
     if (const char* e = getenv("OAZ_CONV_RG")) {
         const int v = atoi(e);
@@ -1157,9 +1124,9 @@ extern "C" int oaz_trainer_set_stream(oaz_trainer* t, void* stream) {
 
 static int repack(oaz_trainer* t) {
     for (int l = 0; l < t->nconv; ++l) {
-        const int chunks = l == 0 ? 2 : 4, cin = l == 0 ? kIn : kC;
+        const int chunks = l == 0 ? 2 : 4, cin = (int)t->L.tower[l].cin;
         const int n = 9 * chunks * 256;
-        hipLaunchKernelGGL(k_pack, dim3((n + 255) / 256), dim3(256), 0, t->st, t->P + t->L.cw[l], cin, chunks,
+        hipLaunchKernelGGL(k_pack, dim3((n + 255) / 256), dim3(256), 0, t->st, t->P + t->L.tower[l].w, cin, chunks,
                            t->wf[l], t->wd[l]);
     }
     HIP_TRY(hipGetLastError());
@@ -1244,8 +1211,8 @@ static void launch_conv(int ch, int rg, dim3 grid, hipStream_t st, const ConvArg
 
 static int backward(oaz_trainer* t, int bi) {
     const int B = t->batch, R = B * 25, NB = t->cfg.blocks, nl = t->nconv;
-    const Layout& L = t->L;
-    const HeadOff& h = L.h;
+    const wl::Layout& L = t->L;
+    const HeadOff& h = t->h;
     hipStream_t st = t->st;
     float* P = t->P;
     float* G = t->G;
@@ -1257,10 +1224,11 @@ static int backward(oaz_trainer* t, int bi) {
                        t->X0, t->pi, t->z);
     // ---- forward
     for (int l = 0; l < nl; ++l) {
+        const wl::ConvBn& cv = L.tower[l];
         ConvArgs a{};
         a.in = l == 0 ? t->X0 : t->A[l - 1];
         a.w = t->wf[l];
-        a.bias = P + L.cb[l];
+        a.bias = P + cv.b;
         a.out = t->Z[l];
         a.part = t->part;
         a.chunks = l == 0 ? 2 : 4;
@@ -1271,14 +1239,14 @@ static int backward(oaz_trainer* t, int bi) {
         if (t->cfin) {
             const unsigned nwg_act = t->cfin > 0 ? (unsigned)t->cfin : (unsigned)((n / 4 + 1023) / 1024);
             hipLaunchKernelGGL(k_bn_act_cfin, dim3(nwg_act), dim3(1024), 0, st, t->part, nwg_conv, (double)R,
-                               P + L.brm[l], P + L.brv[l], bn_mom, eps, t->mean[l], t->invstd[l], t->Z[l],
-                               P + L.bg[l], P + L.bb[l], skip, t->A[l], n);
+                               P + cv.mean, P + cv.var, bn_mom, eps, t->mean[l], t->invstd[l], t->Z[l],
+                               P + cv.gamma, P + cv.beta, skip, t->A[l], n);
             continue;
         }
         hipLaunchKernelGGL(k_bn_fwd_fin, dim3(1), dim3(1024), 0, st, t->part, nwg_conv, 64, 0, 64, (double)R,
-                           P + L.brm[l], P + L.brv[l], bn_mom, eps, t->mean[l], t->invstd[l], 64, nullptr, nullptr);
+                           P + cv.mean, P + cv.var, bn_mom, eps, t->mean[l], t->invstd[l], 64, nullptr, nullptr);
         hipLaunchKernelGGL(k_bn_act, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, t->Z[l], t->mean[l],
-                           t->invstd[l], P + L.bg[l], P + L.bb[l], skip, t->A[l], n);
+                           t->invstd[l], P + cv.gamma, P + cv.beta, skip, t->A[l], n);
     }
     (void)NB;
     // ---- heads
@@ -1324,13 +1292,14 @@ static int backward(oaz_trainer* t, int bi) {
     bool used[2] = {false, false};
     for (int l = nl - 1; l >= 0; --l) {
         const int k = l & 1;
+        const wl::ConvBn& cv = L.tower[l];
         float* c1 = t->bcoef;
         float* mm = t->bcoef + 64;
         float* mx = t->bcoef + 128;
         float* dz = t->DZ[k];
         if (used[k]) HIP_TRY(hipStreamWaitEvent(st, t->ev_w[k], 0));
         hipLaunchKernelGGL(k_bn_bwd_fin, dim3(1), dim3(1024), 0, st, t->part, nwg_part, 64, 0, 64, (double)R,
-                           P + L.bg[l], t->invstd[l], G + L.bg[l], G + L.bb[l], c1, mm, mx, 64, nullptr,
+                           P + cv.gamma, t->invstd[l], G + cv.gamma, G + cv.beta, c1, mm, mx, 64, nullptr,
                            nullptr, nullptr);
         hipLaunchKernelGGL(k_bn_bwd_apply<kBwdU>, dim3(nwg_bwd), dim3(256), 0, st, t->M[l], t->Z[l], t->mean[l],
                            t->invstd[l], c1, mm, mx, dz, t->bpart[k], R);
@@ -1345,11 +1314,11 @@ static int backward(oaz_trainer* t, int bi) {
                 hipLaunchKernelGGL(k_wgrad<1>, dim3(25, 9, kWSplit), dim3(256), 0, t->st2, dz, X, B, t->wpart);
             else
                 hipLaunchKernelGGL(k_wgrad<2>, dim3(25, 9, kWSplit), dim3(256), 0, t->st2, dz, X, B, t->wpart);
-            const int cin = l == 0 ? kIn : kC;
+            const int cin = (int)cv.cin;
             const int nred = 9 * kC * cin;
             hipLaunchKernelGGL(k_wgrad_reduce, dim3((nred + 255) / 256), dim3(256), 0, t->st2, t->wpart,
-                               l == 0 ? kInPad : kC, cin, G + L.cw[l]);
-            hipLaunchKernelGGL(k_colsum, dim3(1), dim3(1024), 0, t->st2, t->bpart[k], nwg_bwd, 64, 0, 64, G + L.cb[l]);
+                               l == 0 ? kInPad : kC, cin, G + cv.w);
+            hipLaunchKernelGGL(k_colsum, dim3(1), dim3(1024), 0, t->st2, t->bpart[k], nwg_bwd, 64, 0, 64, G + cv.b);
             HIP_TRY(hipEventRecord(t->ev_w[k], t->st2));
             used[k] = true;
             return 0;
@@ -1404,8 +1373,8 @@ static int apply(oaz_trainer* t, float scale) {
     ConvTab tab{};
     tab.n = t->nconv;
     for (int l = 0; l < t->nconv; ++l) {
-        tab.off[l] = (int)t->L.cw[l];
-        tab.cin[l] = l == 0 ? kIn : kC;
+        tab.off[l] = (int)t->L.tower[l].w;
+        tab.cin[l] = (int)t->L.tower[l].cin;
         tab.wf[l] = reinterpret_cast<float*>(t->wf[l].get());
         tab.wd[l] = reinterpret_cast<float*>(t->wd[l].get());
     }
@@ -1416,22 +1385,18 @@ static int apply(oaz_trainer* t, float scale) {
 }
 
 // BN running statistics <-> one contiguous range (data-parallel epoch-end average over ranks).
-// Segments: per conv layer running_mean[64] running_var[64] (adjacent in the canonical blob), then
-// the value head's (1 + 1) and the policy head's (2 + 2).
+// Segments (wl::running_stat_runs): per conv layer running_mean[64] running_var[64] (adjacent in the
+// canonical blob), then the value head's (1 + 1) and the policy head's (2 + 2).
 struct BnSegs {
     int n;
     int off[kMaxConv + 2], len[kMaxConv + 2];
 };
 static BnSegs bn_segs(const oaz_trainer* t) {
     BnSegs s{};
-    for (int l = 0; l < t->nconv; ++l) {
-        s.off[s.n] = (int)t->L.brm[l];
-        s.len[s.n++] = 2 * kC;
+    for (const wl::Run& r : wl::running_stat_runs(t->L)) {  // nconv + 2 runs, nconv <= kMaxConv (oaz_trainer_create)
+        s.off[s.n] = (int)r.offset;
+        s.len[s.n++] = (int)r.len;
     }
-    s.off[s.n] = t->L.h.vrm;
-    s.len[s.n++] = 2;
-    s.off[s.n] = t->L.h.prm;
-    s.len[s.n++] = 4;
     return s;
 }
 __global__ void k_bn_stats_io(float* P, float* buf, BnSegs s, int unpack, float scale) {
@@ -1445,7 +1410,11 @@ __global__ void k_bn_stats_io(float* P, float* buf, BnSegs s, int unpack, float 
     }
 }
 
-extern "C" size_t oaz_trainer_bn_stats_count(int blocks) { return (size_t)(1 + 2 * blocks) * 2 * kC + 2 + 4; }
+extern "C" size_t oaz_trainer_bn_stats_count(int blocks) {
+    size_t n = 0;
+    for (const wl::Run& r : wl::running_stat_runs(wl::layout(blocks))) n += r.len;
+    return n;
+}
 
 extern "C" int oaz_trainer_bn_stats_pack(oaz_trainer* t, float* dev_out) {
     if (!t || !dev_out) return oaz_set_err(OAZ_ERR_ARG, "trainer: null");

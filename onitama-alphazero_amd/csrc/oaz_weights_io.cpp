@@ -2,9 +2,9 @@
 // `vs.load(model_path)` in AlphaZeroMcts::from_model_file, alphazero-training/src/alphazero_mcts/
 // mod.rs:89-105, on the ConvResNet built by net.rs:101-213).
 //
-//  * the canonical tensor table: the VarStore names net.rs creates, in creation order, with their
-//    element counts (tch joins path components with '.' in memory and writes '|' into .ot files;
-//    both spellings are accepted);
+//  * the canonical tensor table (oaz_weights_layout.h): the VarStore names net.rs creates, in
+//    creation order, with their shapes (tch joins path components with '.' in memory and writes '|'
+//    into .ot files; both spellings are accepted);
 //  * named loading: a host hands over its variables as (name, data, numel) triples in any order
 //    (e.g. tch's `vs.variables()` HashMap) and they are placed by name, every missing, duplicate,
 //    unknown or wrongly sized tensor failing the load (Q13: the reference keeps its random weights
@@ -26,51 +26,12 @@
 
 #include "../../include/onitama_az.h"
 #include "oaz_host.h"
+#include "oaz_weights_layout.h"
 
 namespace {
 
-struct TensorSpec {
-    std::string name;  // '|'-joined, as in the .ot files
-    size_t numel;
-    std::vector<size_t> shape;  // the tch shape (net.rs) the .ot writer records
-};
-
-// net.rs:101-213, in VarStore creation order (= oaz_weight_count's blob layout).
-std::vector<TensorSpec> canonical_layout(int blocks) {
-    std::vector<TensorSpec> v;
-    const size_t C = 64, I = 21;
-    auto add = [&](const std::string& n, std::vector<size_t> shape) {
-        size_t numel = 1;
-        for (size_t d : shape) numel *= d;
-        v.push_back({n, numel, std::move(shape)});
-    };
-    auto conv = [&](const std::string& n, size_t cout, size_t cin, size_t k) {
-        add(n + "|weight", {cout, cin, k, k});
-        add(n + "|bias", {cout});
-    };
-    auto bn = [&](const std::string& n, size_t c) {
-        for (const char* f : {"weight", "bias", "running_mean", "running_var"}) add(n + "|" + f, {c});
-    };
-    conv("conv_init_1", C, I, 3);
-    bn("bn1", C);
-    for (int i = 0; i < blocks; ++i)
-        for (int j = 1; j <= 2; ++j) {
-            const std::string p = "resnet_" + std::to_string(i) + "|resnet_small_block" + std::to_string(j);
-            conv(p + "|small_block_conv", C, C, 3);
-            bn(p + "|small_block_bn", C);
-        }
-    conv("vh_conv", 1, C, 1);
-    bn("vh_bn", 1);
-    add("vh_linear1|weight", {C, 25});
-    add("vh_linear1|bias", {C});
-    add("vh_linear2|weight", {1, C});
-    add("vh_linear2|bias", {1});
-    conv("policy_conv", 2, C, 1);
-    bn("policy_bn", 2);
-    add("ph_linear2|weight", {50, 50});
-    add("ph_linear2|bias", {50});
-    return v;
-}
+using oaz::wl::Layout;
+using oaz::wl::Tensor;
 
 std::string normalise(const char* n) {
     std::string s(n);
@@ -94,17 +55,17 @@ int blocks_of(const std::vector<std::string>& names, int* out) {
     return 0;
 }
 
-int assemble(int blocks, const std::vector<std::string>& names, const std::vector<const float*>& data,
+int assemble(const Layout& L, const std::vector<std::string>& names, const std::vector<const float*>& data,
              const std::vector<size_t>& sizes, float* out, size_t cap) {
-    const auto layout = canonical_layout(blocks);
-    const size_t need = oaz_weight_count(blocks, 64, 21);
-    if (!out || cap < need) return oaz_set_err(OAZ_ERR_ARG, "weights: output holds %zu floats, need %zu", cap, need);
+    const int blocks = L.blocks;
+    if (!out || cap < L.total)
+        return oaz_set_err(OAZ_ERR_ARG, "weights: output holds %zu floats, need %zu", cap, L.total);
     std::map<std::string, size_t> at;
     for (size_t i = 0; i < names.size(); ++i)
         if (!at.emplace(names[i], i).second)
             return oaz_set_err(OAZ_ERR_WEIGHTS, "weights: tensor '%s' given twice", names[i].c_str());
-    size_t off = 0, used = 0;
-    for (const auto& t : layout) {
+    size_t used = 0;
+    for (const Tensor& t : L.tensors) {
         auto it = at.find(t.name);
         if (it == at.end())  // VarStore::load: TensorNameNotFound
             return oaz_set_err(OAZ_ERR_WEIGHTS, "weights: missing tensor '%s' (%d-block ResNet, net.rs:101-213)",
@@ -114,19 +75,17 @@ int assemble(int blocks, const std::vector<std::string>& names, const std::vecto
             return oaz_set_err(OAZ_ERR_WEIGHTS, "weights: tensor '%s' has %zu elements, expected %zu", t.name.c_str(),
                                sizes[i], t.numel);
         if (!data[i]) return oaz_set_err(OAZ_ERR_ARG, "weights: tensor '%s' has no data", t.name.c_str());
-        memcpy(out + off, data[i], t.numel * sizeof(float));
-        off += t.numel;
+        memcpy(out + t.offset, data[i], t.numel * sizeof(float));
         ++used;
     }
     if (used != names.size())
         for (const auto& n : names) {
             bool known = false;
-            for (const auto& t : layout) known = known || t.name == n;
+            for (const Tensor& t : L.tensors) known = known || t.name == n;
             if (!known)
                 return oaz_set_err(OAZ_ERR_WEIGHTS, "weights: tensor '%s' is not part of a %d-block ResNet", n.c_str(),
                                    blocks);
         }
-    if (off != need) return oaz_set_err(OAZ_ERR_STATE, "weights: layout mismatch");
     return 0;
 }
 
@@ -553,8 +512,9 @@ int read_ot(const char* path, int* blocks_out, std::vector<float>* blob) {
     std::vector<const float*> data;
     std::vector<size_t> sizes;
     for (const auto& v : vals) data.push_back(v.data()), sizes.push_back(v.size());
-    blob->assign(oaz_weight_count(blocks, 64, 21), 0.0f);
-    if (int rc = assemble(blocks, names, data, sizes, blob->data(), blob->size())) return rc;
+    const Layout L = oaz::wl::layout(blocks);
+    blob->assign(L.total, 0.0f);
+    if (int rc = assemble(L, names, data, sizes, blob->data(), blob->size())) return rc;
     *blocks_out = blocks;
     return 0;
 }
@@ -616,12 +576,12 @@ void pk_int(Bytes& o, size_t v) {
     }
 }
 
-std::string data_pkl(const std::vector<TensorSpec>& layout) {
+std::string data_pkl(const std::vector<Tensor>& layout) {
     Bytes o;
     o.str(std::string("\x80\x02", 2));
     o.str("c__torch__\nModule\n)\x81}(");
     for (size_t i = 0; i < layout.size(); ++i) {
-        const TensorSpec& t = layout[i];
+        const Tensor& t = layout[i];
         pk_str(o, t.name);
         o.str("ctorch._utils\n_rebuild_tensor_v2\n(");
         o.str("(");  // persistent id: ('storage', FloatStorage, key, location, numel)
@@ -647,7 +607,7 @@ std::string data_pkl(const std::vector<TensorSpec>& layout) {
     return o.b;
 }
 
-std::string torch_py(const std::vector<TensorSpec>& layout) {
+std::string torch_py(const std::vector<Tensor>& layout) {
     std::string s = "class Module(Module):\n  __parameters__ = [";
     for (const auto& t : layout) s += "\"" + t.name + "\", ";
     s += "]\n  __buffers__ = []\n  __annotations__ = []\n";
@@ -700,9 +660,10 @@ struct ZipWriter {
 };
 
 int write_ot(const char* path, const float* blob, size_t n, int blocks) {
-    const auto layout = canonical_layout(blocks);
-    const size_t need = oaz_weight_count(blocks, 64, 21);
-    if (n != need) return oaz_set_err(OAZ_ERR_ARG, "ot_write: %zu floats given, a %d-block network has %zu", n, blocks, need);
+    const Layout L = oaz::wl::layout(blocks);
+    const std::vector<Tensor>& layout = L.tensors;
+    if (n != L.total)
+        return oaz_set_err(OAZ_ERR_ARG, "ot_write: %zu floats given, a %d-block network has %zu", n, blocks, L.total);
     std::string stem(path);
     const size_t slash = stem.find_last_of('/');
     if (slash != std::string::npos) stem = stem.substr(slash + 1);
@@ -710,16 +671,14 @@ int write_ot(const char* path, const float* blob, size_t n, int blocks) {
     if (dot != std::string::npos && dot > 0) stem = stem.substr(0, dot);
     if (stem.empty()) return oaz_set_err(OAZ_ERR_ARG, "ot_write: bad path '%s'", path);
     ZipWriter z;
-    size_t off = 0;
     std::vector<uint8_t> le;
     for (size_t i = 0; i < layout.size(); ++i) {
         le.resize(layout[i].numel * 4);
         for (size_t e = 0; e < layout[i].numel; ++e) {  // little-endian fp32
             uint32_t u;
-            memcpy(&u, blob + off + e, 4);
+            memcpy(&u, blob + layout[i].offset + e, 4);
             for (int k = 0; k < 4; ++k) le[4 * e + k] = (uint8_t)(u >> (8 * k));
         }
-        off += layout[i].numel;
         z.add(stem + "/data/" + std::to_string(i), le.data(), le.size());
     }
     const std::string pkl = data_pkl(layout), code = torch_py(layout);
@@ -748,12 +707,12 @@ int write_ot(const char* path, const float* blob, size_t n, int blocks) {
 }  // namespace
 
 extern "C" size_t oaz_weight_tensor_count(int blocks) {
-    return blocks < 0 ? 0 : canonical_layout(blocks).size();
+    return blocks < 0 ? 0 : oaz::wl::layout(blocks).tensors.size();
 }
 
 extern "C" int oaz_weight_tensor_info(int blocks, size_t i, char* name, size_t name_cap, size_t* numel) {
     if (blocks < 0) return oaz_set_err(OAZ_ERR_ARG, "weight_tensor_info: blocks < 0");
-    const auto layout = canonical_layout(blocks);
+    const std::vector<Tensor> layout = oaz::wl::layout(blocks).tensors;
     if (i >= layout.size()) return oaz_set_err(OAZ_ERR_ARG, "weight_tensor_info: index %zu of %zu", i, layout.size());
     if (numel) *numel = layout[i].numel;
     if (name) {
@@ -771,7 +730,7 @@ extern "C" int oaz_weights_from_named(int blocks, const char* const* names, cons
         if (!names[i]) return oaz_set_err(OAZ_ERR_ARG, "weights_from_named: name %zu is null", i);
         nm.push_back(normalise(names[i]));
     }
-    return assemble(blocks, nm, std::vector<const float*>(data, data + n), std::vector<size_t>(sizes, sizes + n), out,
+    return assemble(oaz::wl::layout(blocks), nm, std::vector<const float*>(data, data + n), std::vector<size_t>(sizes, sizes + n), out,
                     out_n);
 }
 
@@ -779,7 +738,7 @@ extern "C" int oaz_load_weights_named(oaz_engine* e, const char* const* names, c
                                       const size_t* sizes, size_t n) {
     oaz_config cfg;
     if (int rc = oaz_get_config(e, &cfg)) return rc;
-    std::vector<float> blob(oaz_weight_count(cfg.blocks, 64, 21));
+    std::vector<float> blob(oaz::wl::layout(cfg.blocks).total);
     if (int rc = oaz_weights_from_named(cfg.blocks, names, data, sizes, n, blob.data(), blob.size())) return rc;
     return oaz_load_weights(e, blob.data(), blob.size());
 }

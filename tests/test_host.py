@@ -79,6 +79,19 @@ def test_weight_layout(lib, orc, blocks):
     assert np.array_equal(W.blob_from_named(named, blocks), w)
 
 
+def test_random_weights_bytes():
+    """oaz_random_weights draws in blob order, one draw per weight or bias element: its bytes equal those
+    recorded before the order moved into csrc/oaz_weights_layout.h (tests/golden/random_weights_digests.json)."""
+    import hashlib
+    import json
+    cases = json.loads((ROOT / "tests" / "golden" / "random_weights_digests.json").read_text())["cases"]
+    assert [(c["seed"], c["blocks"]) for c in cases] == [(20260101, 0), (0, 3), (20260106, 6)]
+    for c in cases:
+        w = W.random_weights(c["seed"], c["blocks"])
+        assert w.size == c["floats"]
+        assert hashlib.sha256(w.astype("<f4").tobytes()).hexdigest() == c["sha256"], (c["seed"], c["blocks"])
+
+
 def test_param_counts_match_survey():  # SURVEY.md 0 and 8a-A7
     assert W.weight_count(3) == 240_006 and W.weight_count(5) == 388_742 and W.weight_count(6) == 463_110
 

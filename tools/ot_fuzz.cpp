@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../include/onitama_az.h"
+#include "../onitama-alphazero_amd/csrc/oaz_weights_layout.h"
 
 // ---- stubs for the symbols oaz_weights_io.cpp takes from oaz_engine.cpp ----------------------
 int oaz_set_err(int code, const char* fmt, ...) {
@@ -22,15 +23,6 @@ int oaz_set_err(int code, const char* fmt, ...) {
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     return code;
-}
-// same formula as oaz_engine.cpp (the reader checks its own canonical table against it)
-extern "C" size_t oaz_weight_count(int blocks, int channels, int in_planes) {
-    const size_t C = (size_t)channels, I = (size_t)in_planes;
-    size_t n = C * I * 9 + C + 4 * C;
-    n += (size_t)blocks * 2 * (C * C * 9 + C + 4 * C);
-    n += C + 1 + 4 + C * 25 + C + C + 1;
-    n += 2 * C + 2 + 8 + 50 * 50 + 50;
-    return n;
 }
 extern "C" int oaz_get_config(const oaz_engine*, oaz_config*) { return OAZ_ERR_ARG; }
 extern "C" int oaz_load_weights(oaz_engine*, const float*, size_t) { return OAZ_ERR_ARG; }
@@ -51,7 +43,7 @@ extern "C" int LLVMFuzzerTestOneInput(const uint8_t* data, size_t size) {
     int blocks = -1;
     if (oaz_ot_read(g_path, nullptr, 0, &n, &blocks) == 0) {
         // accepted: the blob must be exactly a canonical network of the reported block count
-        if (blocks < 0 || blocks > 64 || n != oaz_weight_count(blocks, 64, 21)) abort();
+        if (blocks < 0 || blocks > 64 || n != oaz::wl::layout(blocks).total) abort();
         std::vector<float> out(n);
         size_t n2 = 0;
         if (oaz_ot_read(g_path, out.data(), out.size(), &n2, nullptr) != 0 || n2 != n) abort();
