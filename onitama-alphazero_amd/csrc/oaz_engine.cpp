@@ -257,11 +257,24 @@ extern "C" int oaz_encode(const oaz_state* s, int n, float* planes) {
 // ---- engine ------------------------------------------------------------------------------------
 constexpr int kMaxParts = 4;  // run_sims: game parts, each on its own stream (oaz_config.parts)
 
+// What a timed launch counts as in oaz_kernel_times (accumulate's table is in this order).
+// K_NOISE: the root noise (second stream); K_COMPACT: leaf compaction; K_BACKUP_SELECT: expand/backup + next
+// select (fused), and the one-launch searches.
+enum LaunchKind { K_SELECT, K_NN, K_EXPAND, K_FINALIZE, K_NOISE, K_COMPACT, K_BACKUP_SELECT, K_COUNT };
+
 struct TimedLaunch {
-    int kind;  // 0 select, 1 nn, 2 expand, 3 finalize, 4 root noise (second stream), 5 leaf compaction,
-               // 6 expand/backup + next select (fused)
+    LaunchKind kind;
     Event a, b;
     uint32_t samples;
+};
+
+// The facts about the last run_sims (oaz_last_sims, oaz_search_playouts).
+struct LastSearch {
+    uint32_t G = 0;                  // its games
+    uint32_t sims = 0;               // simulations per game (Q7 budget: may be < cfg.sims)
+    bool on_device = false;          // Q7 on the device: each game's count is still in sims_run; fetch_sims_run
+                                     // reads them once into per_game, and sims is then their maximum
+    std::vector<uint32_t> per_game;  // (empty: every game ran `sims`)
 };
 
 // The device resources are owning members (oaz_host.h), destroyed in reverse declaration order after
@@ -296,17 +309,12 @@ struct oaz_engine {
     DevBuf<oaz_move> s_move;
     DevBuf<float> s_pi, s_rootv, s_rootp;
     uint32_t search_calls = 0;
-    uint32_t last_sims = 0;  // simulations per game of the last run_sims (Q7 budget: may be < cfg.sims)
-    // Q7 on the device (the one-launch searches): the deadline on the device clock, each game's simulation
-    // count (last_sims_dev: the last run_sims wrote them for its last_G games; last_sims is then their maximum)
+    LastSearch last;
+    // Q7 on the device (the one-launch searches): the deadline on the device clock, each game's simulation count
     DevBuf<uint64_t> deadline;
     DevBuf<uint32_t> sims_run;
     int wall_khz = 0;  // hipDeviceAttributeWallClockRate (kHz)
-    bool last_sims_dev = false;
-    bool deadline_armed = false;  // begin_budget launched k_deadline_start for the current search / ply
-    double t_search0 = 0.0;       // host clock at the start of the current search / ply (0: no budget)
-    uint32_t last_G = 0;
-    std::vector<uint32_t> sims_host;  // per-game counts of the last device-budgeted run (empty: all last_sims)
+    double t_search0 = 0.0;  // host clock at the start of the current search / ply (0: no budget)
     DevBuf<uint32_t> s_ply;
     // self-play
     DevBuf<oaz_state> root;
@@ -406,16 +414,17 @@ static Event ev_get(oaz_engine* e) {
 #define OAZ_NOISE_CHUNK 16
 #endif
 static constexpr uint32_t kNoiseChunk = OAZ_NOISE_CHUNK;  // simulations of root noise produced per launch
-static uint32_t noise_chunk_for(const oaz_engine* e);  // after grp_search
+static uint32_t noise_chunk_for(const oaz_engine* e);  // after search_path
 
 static void accumulate(oaz_engine* e, const TimedLaunch& p, float ms) {
-    double* acc[7] = {&e->times.select_ms, &e->times.nn_ms, &e->times.expand_ms, &e->times.finalize_ms,
-                      &e->times.noise_ms, &e->times.compact_ms, &e->times.backup_select_ms};
-    uint64_t* cnt[7] = {&e->times.select_n, &e->times.nn_n, &e->times.expand_n, &e->times.finalize_n,
-                        &e->times.noise_n, &e->times.compact_n, &e->times.backup_select_n};
-    *acc[p.kind] += ms;
-    *cnt[p.kind] += 1;
-    if (p.kind == 1) e->times.nn_samples += p.samples;
+    oaz_kernel_times& t = e->times;
+    const struct { double* ms; uint64_t* n; } of[K_COUNT] = {
+        {&t.select_ms, &t.select_n},     {&t.nn_ms, &t.nn_n},       {&t.expand_ms, &t.expand_n},
+        {&t.finalize_ms, &t.finalize_n}, {&t.noise_ms, &t.noise_n}, {&t.compact_ms, &t.compact_n},
+        {&t.backup_select_ms, &t.backup_select_n}};
+    *of[p.kind].ms += ms;
+    *of[p.kind].n += 1;
+    if (p.kind == K_NN) t.nn_samples += p.samples;
 }
 
 // Resolve the recorded event pairs: per-kind sums, and the NN's busy time = the length of the union
@@ -428,7 +437,7 @@ static int resolve_pending(oaz_engine* e) {
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, p.a, p.b));
         accumulate(e, p, ms);
-        if (p.kind == 1) {
+        if (p.kind == K_NN) {
             float t0 = 0.f;
             HIP_TRY(hipEventElapsedTime(&t0, ref, p.a));
             nn.emplace_back(t0, t0 + ms);
@@ -465,7 +474,7 @@ static int resolve_timing(oaz_engine* e) {
 }
 
 template <class F>
-static int timed(oaz_engine* e, int kind, uint32_t samples, F&& launch, hipStream_t st = nullptr) {
+static int timed(oaz_engine* e, LaunchKind kind, uint32_t samples, F&& launch, hipStream_t st = nullptr) {
     if (!st) st = e->stream;
     if (!e->timing || e->timing_skip) {
         HIP_TRY(launch());
@@ -609,34 +618,33 @@ extern "C" int oaz_set_search_time(oaz_engine* e, int64_t search_time_ns) {
 
 // The device-budgeted searches leave each game's count on the device; read them once.
 static int fetch_sims_run(oaz_engine* e) {
-    if (!e->last_sims_dev) return 0;
+    LastSearch& L = e->last;
+    if (!L.on_device) return 0;
     OAZ_ON_DEVICE(e->device);
-    std::vector<uint32_t> n(e->last_G);
-    if (e->last_G) {
-        HIP_TRY(hipMemcpyAsync(n.data(), e->sims_run, (size_t)e->last_G * 4, hipMemcpyDeviceToHost, e->stream));
+    std::vector<uint32_t> n(L.G);
+    if (L.G) {
+        HIP_TRY(hipMemcpyAsync(n.data(), e->sims_run, (size_t)L.G * 4, hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
-    uint32_t m = 0;
-    for (uint32_t v : n) m = v > m ? v : m;
-    e->last_sims = m;
-    e->last_sims_dev = false;
-    e->sims_host = std::move(n);
+    L.sims = n.empty() ? 0 : *std::max_element(n.begin(), n.end());
+    L.on_device = false;
+    L.per_game = std::move(n);
     return 0;
 }
 
 extern "C" int oaz_last_sims(oaz_engine* e, int* sims) {
     if (!e || !sims) return oaz_set_err(OAZ_ERR_ARG, "last_sims: null");
     if (int rc = fetch_sims_run(e)) return rc;
-    *sims = (int)e->last_sims;
+    *sims = (int)e->last.sims;
     return 0;
 }
 
 extern "C" int oaz_search_playouts(oaz_engine* e, int* out, int G) {
     if (!e || (!out && G > 0) || G < 0) return oaz_set_err(OAZ_ERR_ARG, "search_playouts: bad arguments");
-    if ((uint32_t)G > e->last_G)
-        return oaz_set_err(OAZ_ERR_ARG, "search_playouts: G=%d > %u games in the last search", G, e->last_G);
+    if ((uint32_t)G > e->last.G)
+        return oaz_set_err(OAZ_ERR_ARG, "search_playouts: G=%d > %u games in the last search", G, e->last.G);
     if (int rc = fetch_sims_run(e)) return rc;
-    for (int g = 0; g < G; ++g) out[g] = e->sims_host.empty() ? (int)e->last_sims : (int)e->sims_host[(size_t)g];
+    for (int g = 0; g < G; ++g) out[g] = (int)(e->last.per_game.empty() ? e->last.sims : e->last.per_game[(size_t)g]);
     return 0;
 }
 
@@ -719,9 +727,9 @@ static int evaluate(oaz_engine* e, const oaz_state* d_states, uint32_t B, float*
     if (!st) st = e->stream;
     const uint32_t counted = tm ? 0u : B;  // compacted: the count is on the device (GS_EVALS)
     if (e->cfg.evaluator == OAZ_EVAL_HASH)
-        return timed(e, 1, counted, [&] { return launch_hash_eval(d_states, (int)B, d_pol, d_val, st); }, st);
+        return timed(e, K_NN, counted, [&] { return launch_hash_eval(d_states, (int)B, d_pol, d_val, st); }, st);
     const NNView w = nn_view(e, tm);
-    return timed(e, 1, counted, [&] { return launch_nn_forward(w, d_states, (int)B, d_pol, d_val, st); }, st);
+    return timed(e, K_NN, counted, [&] { return launch_nn_forward(w, d_states, (int)B, d_pol, d_val, st); }, st);
 }
 
 extern "C" int oaz_nn_fallbacks(oaz_engine* e, uint64_t* tiles) {
@@ -747,6 +755,7 @@ extern "C" int oaz_nn_forward(oaz_engine* e, const oaz_state* s, int B, float* p
     return 0;
 }
 
+// ---- the search driver (run_sims) -------------------------------------------------------------------
 // Leaf compaction (oaz_config.compact; off by default: every playout evaluates its leaf, Q2) pays
 // when it can remove whole rounds of NN workgroups (one 16-position tile per
 // CU at a time): at C3 the ~8.7 % won leaves are 1.4 of 16 rounds. Below 12 rounds (G < 12 * 16 *
@@ -756,24 +765,23 @@ static bool compact_leaves(const oaz_engine* e, uint32_t G) {
     return e->cfg.compact == 1 || (e->cfg.compact == 2 && G >= 12u * 16u * (uint32_t)e->cus);
 }
 
-// What both one-launch searches (oaz_search_lat.hip) need: the segmented tree kernels they are built from, every
-// leaf evaluated in place, and an evaluator they contain (HASH, or the fp16x3 network).
-static bool one_launch_search(const oaz_engine* e, uint32_t G) {
-    return e->cfg.step_kernels == 0 && !compact_leaves(e, G) &&
-           (e->cfg.evaluator == OAZ_EVAL_HASH || e->cfg.precision == OAZ_FP32_SPLIT16) && tree_seg_kernels();
-}
-
-// A search of G games runs as k_search_grp launches (16 games per workgroup, up to one round of workgroups,
-// one launch per root-noise chunk) instead of the per-simulation-step launches. Everything it depends on is
-// fixed at creation except G (any G below a qualifying engine's qualifies as well).
-static bool grp_search(const oaz_engine* e, uint32_t G) {
-    return one_launch_search(e, G) && (G + 15) / 16 <= (uint32_t)e->cus;
-}
-
-// k_search_lat: a workgroup per game runs all its simulations in one launch, when the per-step loop would
-// launch one NN workgroup per game anyway and nothing needs a second stream (the root noise) between steps.
-static bool lat_search(const oaz_engine* e, uint32_t G, bool noise) {
-    return one_launch_search(e, G) && !noise && G <= (uint32_t)e->cus;
+// How a search of G games runs. Both one-launch searches (oaz_search_lat.hip) need the segmented tree kernels
+// they are built from, every leaf evaluated in place, and an evaluator they contain (HASH, or the fp16x3
+// network); everything they depend on is fixed at creation except G and the noise.
+//   LAT    k_search_lat: a workgroup per game runs all its simulations in one launch, when the per-step loop
+//          would launch one NN workgroup per game anyway and nothing needs a second stream (the root noise)
+//          between steps;
+//   GRP    k_search_grp: 16 games per workgroup, up to one round of workgroups, one launch per root-noise
+//          chunk (any G below a qualifying engine's qualifies as well);
+//   STEPS  the per-simulation-step launches.
+enum SearchPath { PATH_LAT, PATH_GRP, PATH_STEPS };
+static SearchPath search_path(const oaz_engine* e, uint32_t G, bool noise) {
+    const bool one_launch = e->cfg.step_kernels == 0 && !compact_leaves(e, G) &&
+                            (e->cfg.evaluator == OAZ_EVAL_HASH || e->cfg.precision == OAZ_FP32_SPLIT16) &&
+                            tree_seg_kernels();
+    if (!one_launch) return PATH_STEPS;
+    if (!noise && G <= (uint32_t)e->cus) return PATH_LAT;
+    return (G + 15) / 16 <= (uint32_t)e->cus ? PATH_GRP : PATH_STEPS;
 }
 
 // Simulations per root-noise ring slot. An engine whose searches run as k_search_grp: every chunk is one
@@ -783,288 +791,24 @@ static bool lat_search(const oaz_engine* e, uint32_t G, bool noise) {
 // noise overlaps the network and the first select waits for only 16 simulations' draws. Ring: 2 x chunk x
 // G x 80 floats (<= 1.3 GB at 4 096 games).
 static uint32_t noise_chunk_for(const oaz_engine* e) {
-    if (!grp_search(e, e->G)) return kNoiseChunk;
-    const uint32_t c = e->sims_cap < 512 ? (uint32_t)e->sims_cap : 512u;
-    return c > kNoiseChunk ? c : kNoiseChunk;
+    if (search_path(e, e->G, true) != PATH_GRP) return kNoiseChunk;
+    return std::max(kNoiseChunk, std::min((uint32_t)e->sims_cap, 512u));
 }
 
-// All cfg.sims simulations of one move for every game, in lock step: select -> leaf compaction ->
-// evaluate -> expand/backup, where simulation s's expand/backup and simulation s+1's select run as
-// one kernel (k_backup_select_seg; a game's next walk needs only its own backup). Select marks the games whose playout uses its leaf evaluation (all
-// but those ending on a won, terminal-flagged node, whose evaluation the reference discards:
-// mcts_arena.rs:156-176) and the compaction kernel packs their leaves per 4096-game bucket, so the
-// network evaluates only those. With root noise, k_root_noise fills chunk c+1 of the
-// double-buffered noise ring on stream2 while stream 1 runs chunk c (events order the ring slots).
-static TreeView slice_view(const TreeView& t, uint32_t g0, uint32_t n, int b0);
-
-// Game parts of run_sims (oaz_config.parts; 0 = auto: two from kAutoParts games; the overlap of
+// Game parts of the per-step loop (oaz_config.parts; 0 = auto: two from kAutoParts games; the overlap of
 // one part's tree kernels and NN tail with the other's launches measured +3-4 % on C2, C3, C5).
 constexpr uint32_t kAutoParts = 2048;
 static int game_parts(const oaz_engine* e, uint32_t G) {
     int p = e->cfg.parts ? e->cfg.parts : (G >= kAutoParts ? 2 : 1);
-#if OAZ_AB  // A/B build only: OAZ_SPLIT_HALVES=n overrides
-    if (const char* v = getenv("OAZ_SPLIT_HALVES")) p = atoi(v);
-#endif
-    if (p != 2 && p != 4) p = 1;
     // every part non-empty: part h starts at h * ceil(G / p), so the last one needs (p - 1) * ceil(G / p) < G
     // (G = 5, p = 4 would give parts of 2, 2, 1 and an empty fourth)
     while (p > 1 && (uint32_t)(p - 1) * ((G + (uint32_t)p - 1) / (uint32_t)p) >= G) p /= 2;
     return p;
 }
 
-// Game range [g0, g0 + n) of part h of nh over G games (clamped: no part extends past G).
-static void part_range(uint32_t G, int nh, int h, uint32_t* g0, uint32_t* n) {
-    const uint32_t Gh = (G + (uint32_t)nh - 1) / (uint32_t)nh;
-    const uint32_t s = std::min((uint32_t)h * Gh, G);
-    *g0 = s;
-    *n = std::min(Gh, G - s);
-}
-
-static int run_sims_body(oaz_engine* e, const TreeView& t, const oaz_state* roots, const uint8_t* active,
-                         const uint64_t* gids, const uint32_t* plies);
-
-// run_sims_body, and on an error the game parts' streams are joined into the engine stream anyway
-// (its early returns skip the join), so oaz_sync and buffer reuse after an error wait for them.
-static int run_sims(oaz_engine* e, const TreeView& t, const oaz_state* roots, const uint8_t* active,
-                    const uint64_t* gids, const uint32_t* plies) {
-    const int rc = run_sims_body(e, t, roots, active, gids, plies);
-    if (rc) {
-        const std::string msg = g_err;
-        for (int h = 1; h < kMaxParts; ++h)
-            if (hipEventRecord(e->ev_part[h], e->stream3[h - 1]) == hipSuccess)
-                (void)hipStreamWaitEvent(e->stream, e->ev_part[h], 0);
-        e->timing_skip = false;
-        g_err = msg;
-    }
-    return rc;
-}
-
-
-// Q7: the device deadline = the device clock when k_deadline_start runs on the engine stream + the budget.
-static int arm_deadline(oaz_engine* e) {
-    if (e->wall_khz <= 0) return oaz_set_err(OAZ_ERR_HIP, "search_time: the device reports no wall clock rate");
-    const double ticks = (double)e->cfg.search_time_ns * (double)e->wall_khz * 1e-6;
-    HIP_TRY(launch_deadline_start(e->deadline, ticks < 1.8e19 ? (uint64_t)ticks : (uint64_t)1.8e19, e->stream));
-    e->deadline_armed = true;
-    return 0;
-}
-
-// Q7: a search's budget runs from the start of the search call, as the reference's Instant is taken at the
-// top of search() (mcts_arena.rs:75-78): the host clock now (the per-step loop's reads) and, on the device,
-// the deadline armed before this search's first upload or reset on the engine stream (the one-launch
-// searches' reads), so the roots upload and the tree reset count against the budget on both paths. Work
-// queued on the stream by earlier calls (asynchronous self-play plies) is not part of this search.
-static int begin_budget(oaz_engine* e) {
-    e->deadline_armed = false;
-    e->t_search0 = 0.0;
-    if (e->cfg.search_time_ns <= 0) return 0;
-    e->t_search0 = now_ns();
-    return e->wall_khz > 0 ? arm_deadline(e) : 0;
-}
-
-static int run_sims_body(oaz_engine* e, const TreeView& t, const oaz_state* roots, const uint8_t* active,
-                         const uint64_t* gids, const uint32_t* plies) {
-    const SearchParams prm = search_params(e);
-    const uint32_t sims = (uint32_t)e->cfg.sims;
-    // Q7 (opt-in, oaz_config.search_time_ns): the reference's loop runs playouts while
-    // `playouts < max_playouts && elapsed < search_time` (mcts_arena.rs:78). The one-launch searches
-    // (k_search_lat, k_search_grp: the Agent / arena sizes) read the device clock before every simulation
-    // and each workgroup stops on its own (oaz_search_playouts: each game's count, >= 1). The per-step loop
-    // (larger batches) advances all games together, so there the clock is read between simulation steps
-    // (after the streams drained) and the search stops after the first step that ends at or past the
-    // budget: every game then has run the same number of playouts (>= 1). pi / the move come from the
-    // visits that ran.
-    const double budget_ns = (double)e->cfg.search_time_ns;
-    const double t_start = budget_ns > 0 ? (e->t_search0 > 0 ? e->t_search0 : now_ns()) : 0.0;
-    e->last_sims = 0;
-    e->last_sims_dev = false;
-    e->sims_host.clear();
-    e->last_G = t.G;
-    // the one-launch searches check the budget on the device (oaz_search_lat.hip): the deadline is the
-    // device clock when k_deadline_start runs + the budget in clock ticks
-    auto device_budget = [&]() -> int {
-        if (budget_ns <= 0) return 0;
-        if (!e->deadline_armed)
-            if (int rc = arm_deadline(e)) return rc;
-        HIP_TRY(hipMemsetAsync(e->sims_run, 0, (size_t)t.G * 4, e->stream));
-        e->last_sims_dev = true;
-        return 0;
-    };
-    uint64_t* const dl = budget_ns > 0 ? e->deadline.get() : nullptr;
-    uint32_t* const sr = budget_ns > 0 ? e->sims_run.get() : nullptr;
-    const bool noise = e->cfg.train_noise && e->noise;
-    const bool hash = e->cfg.evaluator == OAZ_EVAL_HASH;
-    if (lat_search(e, t.G, noise)) {
-        const NNView w = nn_view(e, nullptr);
-        TreeView tl = t;  // rows = game ids (no compaction arrays)
-        tl.need = nullptr;
-        tl.slot = nullptr;
-        e->times.parts = 1;
-        e->timing_skip = false;
-        if (int rc = device_budget()) return rc;
-        if (int rc = timed(e, 6, t.G, [&] {
-                return launch_search_lat(tl, roots, active, prm, (int)sims, hash ? nullptr : &w, e->policy, e->value,
-                                         dl, sr, e->stream);
-            }))
-            return rc;
-        e->last_sims = sims;  // (with a budget: replaced by the games' largest count when it is asked for)
-        return 0;
-    }
-    const uint32_t chunk = e->noise_chunk;
-    const size_t slot_elems = (size_t)chunk * t.G * kNoiseStride;
-    const uint32_t nchunks = (sims + chunk - 1) / chunk;
-    // up to one round of 16-game workgroups (k_search_grp): one launch per noise chunk of simulations,
-    // each workgroup walking, evaluating and backing up its 16 games without a grid-wide step
-    const bool grp = grp_search(e, t.G);
-    // The games in nh parts, each on its own stream: one part's tree kernels, leaf compaction and NN
-    // tail run in the gaps of the others' launches (the NN holds a whole CU per workgroup, so the
-    // tree kernels cannot share a CU with it, only fill the CUs it leaves idle). The parts meet only
-    // through the root-noise ring: chunk c + 2 overwrites chunk c's slot once every part is done with it.
-    const int nh = grp ? 1 : game_parts(e, t.G);
-    if (grp)
-        if (int rc = device_budget()) return rc;
-    auto produce = [&](uint32_t c) -> int {
-        if (c >= 2)
-            for (int h = 0; h < nh; ++h) HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_consumed[c & 1][h], 0));
-        e->timing_skip = false;  // every noise launch is timed (once per chunk)
-        const uint32_t s0 = c * chunk, n = sims - s0 < chunk ? sims - s0 : chunk;
-        noise_t* buf = e->noise + (c & 1) * slot_elems;
-        if (int rc = timed(e, 4, t.G * n, [&] {
-                return launch_root_noise(roots, active, gids, plies, prm, t.G, s0, n, buf, e->stream2);
-            }, e->stream2))
-            return rc;
-        HIP_TRY(hipEventRecord(e->ev_ready[c & 1], e->stream2));
-        return 0;
-    };
-    if (noise) {
-        HIP_TRY(hipEventRecord(e->ev_consumed[0][0], e->stream));  // stream2 starts after prior work
-        HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_consumed[0][0], 0));
-        if (int rc = produce(0)) return rc;
-    }
-    TreeView tc = t;  // the compaction arrays, or none (rows = game ids)
-    if (!compact_leaves(e, t.G)) {
-        tc.need = nullptr;
-        tc.slot = nullptr;
-    }
-#if OAZ_AB  // A/B build only: OAZ_TREE_FUSE=0 runs expand/backup and the next select as two launches
-    static const bool fuse = !(getenv("OAZ_TREE_FUSE") && getenv("OAZ_TREE_FUSE")[0] == '0');
-#else
-    constexpr bool fuse = true;
-#endif
-    const bool split = nh > 1;
-    e->times.parts = (uint64_t)nh;
-    TreeView tv[kMaxParts];
-    uint32_t gstart[kMaxParts] = {0, 0, 0, 0};
-    hipStream_t sh[kMaxParts] = {e->stream, e->stream3[0], e->stream3[1], e->stream3[2]};
-    int b0 = 0;  // a part's compaction bucket counters follow the previous parts'
-    for (int h = 0; h < nh; ++h) {
-        uint32_t n = t.G;
-        part_range(t.G, nh, h, &gstart[h], &n);
-        tv[h] = split ? slice_view(tc, gstart[h], n, b0) : tc;
-        b0 += buckets_of(n);
-    }
-    if (split) {
-        HIP_TRY(hipEventRecord(e->ev_join, e->stream));  // the other streams start after prior work
-        for (int h = 1; h < nh; ++h) HIP_TRY(hipStreamWaitEvent(sh[h], e->ev_join, 0));
-    }
-    auto join = [&]() -> int {  // stream waits for the other parts' streams
-        for (int h = 1; h < nh; ++h) {
-            HIP_TRY(hipEventRecord(e->ev_part[h], sh[h]));
-            HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_part[h], 0));
-        }
-        return 0;
-    };
-    bool out_of_time = false;
-    for (uint32_t c = 0; c < nchunks && !out_of_time; ++c) {
-        if (noise) {
-            if (c + 1 < nchunks)
-                if (int rc = produce(c + 1)) return rc;
-            for (int h = 0; h < nh; ++h) HIP_TRY(hipStreamWaitEvent(sh[h], e->ev_ready[c & 1], 0));
-        }
-        const uint32_t s0 = c * chunk, s1 = s0 + chunk < sims ? s0 + chunk : sims;
-        if (grp) {  // the chunk's simulations in one launch
-            const NNView w = nn_view(e, nullptr);
-            e->timing_skip = false;
-            const noise_t* nz = noise ? e->noise + (c & 1) * slot_elems : nullptr;
-            if (int rc = timed(e, 6, t.G * (s1 - s0), [&] {
-                    return launch_search_grp(tv[0], roots, active, prm, (int)s0, (int)s1, nz, hash ? nullptr : &w,
-                                             e->policy, e->value, dl, sr, sh[0]);
-                }, sh[0]))
-                return rc;
-            e->last_sims = s1;
-        }
-        for (uint32_t s = grp ? s1 : s0; s < s1; ++s) {
-            // Q7: is the budget spent after simulation s - 1? This waits for every part's stream before
-            // each simulation step, so a budgeted search gives up the parts' overlap (and the root-noise
-            // producer runs ahead at most to the step being waited on) and is not the one-launch search:
-            // its throughput is not comparable with an unbudgeted run's (the reference's own cutoff is a
-            // clock read per playout, mcts_arena.rs:78). Parity runs and the benches leave it off.
-            if (budget_ns > 0 && s > 0) {
-                for (int h = 0; h < nh; ++h) HIP_TRY(hipStreamSynchronize(sh[h]));
-                if (now_ns() - t_start >= budget_ns) {
-                    out_of_time = true;
-                    break;
-                }
-            }
-            e->last_sims = s + 1;
-            // sampled steps sit mid-chunk: a chunk's first select also waits for its noise
-            e->timing_skip = e->timing_every > 1 && s % (uint32_t)e->timing_every != (uint32_t)e->timing_every / 2;
-            for (int h = 0; h < nh; ++h) {
-                const TreeView& th = tv[h];
-                const size_t go = gstart[h];
-                if (th.G == 0) continue;
-                const hipStream_t st = sh[h];
-                const oaz_state* rh = roots + go;
-                const uint8_t* ah = active ? active + go : nullptr;  // null in search mode
-                float* pol = e->policy + go * 50;
-                float* val = e->value + go;
-                const noise_t* nz = noise ? e->noise + (c & 1) * slot_elems + ((size_t)(s - s0) * t.G + go) * kNoiseStride
-                                        : nullptr;
-                if (s == 0) {
-                    if (int rc = timed(e, 0, th.G, [&] { return launch_select(th, rh, ah, nz, prm, st); }, st))
-                        return rc;
-                } else if (!fuse) {
-                    if (int rc = timed(e, 2, th.G, [&] { return launch_expand_backup(th, rh, ah, pol, val, st); }, st))
-                        return rc;
-                    if (int rc = timed(e, 0, th.G, [&] { return launch_select(th, rh, ah, nz, prm, st); }, st))
-                        return rc;
-                } else if (int rc = timed(e, 6, th.G, [&] {
-                               return launch_backup_select(th, rh, ah, pol, val, nz, prm, st);
-                           }, st)) {
-                    return rc;
-                }
-                if (th.need) {
-                    // row loads clamped to the part's own rows (the next part's compaction writes its
-                    // rows on another stream)
-                    const TileMap tm{th.bcnt, buckets_of(th.G), (int32_t)th.G};
-                    if (int rc = timed(e, 5, th.G, [&] { return launch_eval_compact(th, st); }, st)) return rc;
-                    if (int rc = evaluate(e, th.cstate, th.G, pol, val, st, &tm)) return rc;
-                } else if (int rc = evaluate(e, th.leaf_state, th.G, pol, val, st)) {
-                    return rc;
-                }
-            }
-        }
-        if (noise)  // this part is done with the noise slot (no join: a part may run a chunk ahead)
-            for (int h = 0; h < nh; ++h) HIP_TRY(hipEventRecord(e->ev_consumed[c & 1][h], sh[h]));
-    }
-    e->timing_skip = false;
-    for (int h = 0; h < nh; ++h) {
-        const size_t go = gstart[h];
-        if (tv[h].G == 0) continue;
-        if (int rc = timed(e, 2, tv[h].G, [&] {
-                return launch_expand_backup(tv[h], roots + go, active ? active + go : nullptr, e->policy + go * 50,
-                                            e->value + go, sh[h]);
-            }, sh[h]))
-            return rc;
-    }
-    if (split)
-        if (int rc = join()) return rc;
-    return 0;
-}
-
 // The trees of games [g0, g0 + n) as a view of their own: every per-game array offset by g0, the
 // part's compaction buckets from bucket counter b0 (its compacted rows start at g0; the NN's row loads
-// are clamped to the part's own n rows by the TileMap cap, run_sims).
+// are clamped to the part's own n rows by the TileMap cap, sim_step).
 static TreeView slice_view(const TreeView& t, uint32_t g0, uint32_t n, int b0) {
     TreeView v = t;
     v.nodes = t.nodes + (size_t)g0 * t.cap;
@@ -1080,6 +824,268 @@ static TreeView slice_view(const TreeView& t, uint32_t g0, uint32_t n, int b0) {
     v.bcnt = t.bcnt + b0;
     v.G = n;
     return v;
+}
+
+// One run_sims call: the trees of all its games, the positions searched and what every launch shares.
+struct Search {
+    TreeView t;              // with the compaction arrays, or none (rows = game ids)
+    const oaz_state* roots;
+    const uint8_t* active;   // null in search mode,
+    const uint64_t* gids;    // as are the game ids
+    const uint32_t* plies;
+    SearchParams prm;
+    uint32_t sims;
+    bool noise;
+    const NNView* net;       // the one-launch searches' network (null: the HASH evaluator)
+    uint64_t* deadline;      // Q7 on the device (the one-launch searches): both null without a budget
+    uint32_t* sims_run;
+};
+
+// The games in n parts, each on its own stream: one part's tree kernels, leaf compaction and NN
+// tail run in the gaps of the others' launches (the NN holds a whole CU per workgroup, so the
+// tree kernels cannot share a CU with it, only fill the CUs it leaves idle). The parts meet only
+// through the root-noise ring. Part h holds games [g0, g0 + t.G): ceil(G / n) each, the last one the rest.
+struct Parts {
+    struct Part {
+        TreeView t;
+        uint32_t g0;
+        hipStream_t st;
+        const oaz_state* roots;
+        const uint8_t* active;
+        float *pol, *val;  // the part's rows of the evaluations
+    };
+    oaz_engine* e;
+    int n;
+    Part part[kMaxParts];
+    Parts(oaz_engine* e, const Search& S, int n) : e(e), n(n) {
+        const uint32_t G = S.t.G, each = (G + (uint32_t)n - 1) / (uint32_t)n;
+        int b0 = 0;  // a part's compaction bucket counters follow the previous parts'
+        for (int h = 0; h < n; ++h) {
+            const uint32_t g0 = (uint32_t)h * each, cnt = std::min(each, G - g0);
+            const hipStream_t st = h ? e->stream3[h - 1] : e->stream;
+            part[h] = {slice_view(S.t, g0, cnt, b0), g0, st, S.roots + g0,
+                       S.active ? S.active + g0 : nullptr, e->policy + (size_t)g0 * 50, e->value + g0};
+            b0 += buckets_of(cnt);
+        }
+    }
+    int fork() const {  // the other parts' streams start after prior work on the engine stream
+        if (n > 1) HIP_TRY(hipEventRecord(e->ev_join, e->stream));
+        for (int h = 1; h < n; ++h) HIP_TRY(hipStreamWaitEvent(part[h].st, e->ev_join, 0));
+        return 0;
+    }
+    int join() const {  // the engine stream waits for the other parts' streams
+        for (int h = 1; h < n; ++h) {
+            HIP_TRY(hipEventRecord(e->ev_part[h], part[h].st));
+            HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_part[h], 0));
+        }
+        return 0;
+    }
+};
+
+// The root-noise ring of one search: e->noise holds two slots of `chunk` simulations' draws for the search's
+// games, chunk c in slot c & 1. k_root_noise fills chunk c + 1 on stream2 while the parts run chunk c, and
+// chunk c + 2 may overwrite chunk c's slot only after every part has released it; the events below carry
+// that rule, so the callers name chunks and simulations, never slots. Without root noise every operation
+// does nothing and at() is null.
+struct NoiseRing {
+    oaz_engine* e;
+    const Search& S;
+    const Parts& P;
+    uint32_t chunk;  // simulations per slot (e->noise_chunk)
+    noise_t* slot(uint32_t c) const { return e->noise + (c & 1) * ((size_t)chunk * S.t.G * kNoiseStride); }
+    const noise_t* at(uint32_t s, uint32_t g0) const {  // simulation s's draws for the games from g0 on
+        return S.noise ? slot(s / chunk) + ((size_t)(s % chunk) * S.t.G + g0) * kNoiseStride : nullptr;
+    }
+    // k_root_noise for chunk c (if the search has one) on stream2: chunk 0 after prior work on the engine
+    // stream, chunk c >= 2 after every part released chunk c - 2
+    int produce(uint32_t c) const {
+        if (!S.noise || c * chunk >= S.sims) return 0;
+        if (c == 0) {
+            HIP_TRY(hipEventRecord(e->ev_consumed[0][0], e->stream));
+            HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_consumed[0][0], 0));
+        } else if (c >= 2) {
+            for (int h = 0; h < P.n; ++h) HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_consumed[c & 1][h], 0));
+        }
+        e->timing_skip = false;  // every noise launch is timed (once per chunk)
+        const uint32_t s0 = c * chunk, n = std::min(S.sims - s0, chunk);
+        if (int rc = timed(e, K_NOISE, S.t.G * n, [&] {
+                return launch_root_noise(S.roots, S.active, S.gids, S.plies, S.prm, S.t.G, s0, n, slot(c), e->stream2);
+            }, e->stream2))
+            return rc;
+        HIP_TRY(hipEventRecord(e->ev_ready[c & 1], e->stream2));
+        return 0;
+    }
+    int wait(uint32_t c) const {  // every part's stream waits for chunk c's draws
+        for (int h = 0; S.noise && h < P.n; ++h) HIP_TRY(hipStreamWaitEvent(P.part[h].st, e->ev_ready[c & 1], 0));
+        return 0;
+    }
+    // every part is done with chunk c at this point of its stream (no join: a part may run a chunk ahead)
+    int release(uint32_t c) const {
+        for (int h = 0; S.noise && h < P.n; ++h) HIP_TRY(hipEventRecord(e->ev_consumed[c & 1][h], P.part[h].st));
+        return 0;
+    }
+};
+
+// Q7: a search's budget runs from the start of the search call (every run_sims follows one of these), as the
+// reference's Instant is taken at the top of search() (mcts_arena.rs:75-78): the host clock now (the per-step
+// loop's reads) and, on the device, the deadline = the device clock when k_deadline_start runs + the budget,
+// armed before this search's first upload or reset on the engine stream (the one-launch searches' reads),
+// so the roots upload and the tree reset count against the budget on both paths. Work queued on the stream
+// by earlier calls (asynchronous self-play plies) is not part of this search.
+static int begin_budget(oaz_engine* e) {
+    e->t_search0 = 0.0;
+    if (e->cfg.search_time_ns <= 0) return 0;
+    e->t_search0 = now_ns();
+    if (e->wall_khz <= 0) return 0;  // (no device clock: only the one-launch searches need it, arm_device_budget)
+    const double ticks = (double)e->cfg.search_time_ns * (double)e->wall_khz * 1e-6;
+    HIP_TRY(launch_deadline_start(e->deadline, ticks < 1.8e19 ? (uint64_t)ticks : (uint64_t)1.8e19, e->stream));
+    return 0;
+}
+
+// Q7 (opt-in, oaz_config.search_time_ns): the reference's loop runs playouts while
+// `playouts < max_playouts && elapsed < search_time` (mcts_arena.rs:78). The one-launch searches
+// (k_search_lat, k_search_grp: the Agent / arena sizes) read the device clock before every simulation
+// and each workgroup stops on its own (oaz_search_playouts: each game's count, >= 1) at begin_budget's
+// deadline; every game's count starts at 0.
+static int arm_device_budget(oaz_engine* e, uint32_t G) {
+    if (e->cfg.search_time_ns <= 0) return 0;
+    if (e->wall_khz <= 0) return oaz_set_err(OAZ_ERR_HIP, "search_time: the device reports no wall clock rate");
+    HIP_TRY(hipMemsetAsync(e->sims_run, 0, (size_t)G * 4, e->stream));
+    e->last.on_device = true;
+    return 0;
+}
+
+// k_search_lat: the whole search in one launch, the last simulation's expand/backup included.
+static int search_lat(oaz_engine* e, const Search& S) {
+    e->times.parts = 1;
+    if (int rc = timed(e, K_BACKUP_SELECT, S.t.G, [&] {
+            return launch_search_lat(S.t, S.roots, S.active, S.prm, (int)S.sims, S.net, e->policy, e->value,
+                                     S.deadline, S.sims_run, e->stream);
+        }))
+        return rc;
+    e->last.sims = S.sims;  // (with a budget: replaced by the games' largest count when it is asked for)
+    return 0;
+}
+
+// k_search_grp: chunk c's simulations in one launch (the one part: every game, on the engine stream), each
+// workgroup walking, evaluating and backing up its 16 games without a grid-wide step.
+static int grp_chunk(oaz_engine* e, const Search& S, const NoiseRing& ring, uint32_t c) {
+    const uint32_t s0 = c * ring.chunk, s1 = std::min(s0 + ring.chunk, S.sims);
+    if (int rc = timed(e, K_BACKUP_SELECT, S.t.G * (s1 - s0), [&] {
+            return launch_search_grp(S.t, S.roots, S.active, S.prm, (int)s0, (int)s1, ring.at(s0, 0), S.net, e->policy,
+                                     e->value, S.deadline, S.sims_run, e->stream);
+        }))
+        return rc;
+    e->last.sims = s1;
+    return 0;
+}
+
+// Simulation step s for every part, in lock step: select -> leaf compaction -> evaluate -> expand/backup,
+// where simulation s - 1's expand/backup and simulation s's select run as one kernel (k_backup_select_seg; a
+// game's next walk needs only its own backup; the last simulation's expand/backup is run_chunks'). Select
+// marks the games whose playout uses its leaf evaluation (all but those ending on a won, terminal-flagged
+// node, whose evaluation the reference discards: mcts_arena.rs:156-176) and the compaction kernel packs their
+// leaves per 4096-game bucket, so the network evaluates only those.
+// Q7 on this loop (larger batches), which advances all games together: the host clock is read between
+// simulation steps and the search stops (*spent) after the first step that ends at or past the budget, so
+// every game has run the same number of playouts (>= 1); pi / the move come from the visits that ran. This
+// waits for every part's stream before each simulation step, so a budgeted search gives up the parts' overlap
+// (and the root-noise producer runs ahead at most to the step being waited on) and is not the one-launch
+// search: its throughput is not comparable with an unbudgeted run's (the reference's own cutoff is a clock
+// read per playout, mcts_arena.rs:78). Parity runs and the benches leave it off.
+static int sim_step(oaz_engine* e, const Search& S, const Parts& P, const NoiseRing& ring, uint32_t s, bool* spent) {
+    if (e->cfg.search_time_ns > 0 && s > 0) {
+        for (int h = 0; h < P.n; ++h) HIP_TRY(hipStreamSynchronize(P.part[h].st));
+        if ((*spent = now_ns() - e->t_search0 >= (double)e->cfg.search_time_ns)) return 0;
+    }
+    e->last.sims = s + 1;
+    // sampled steps sit mid-chunk: a chunk's first select also waits for its noise
+    e->timing_skip = e->timing_every > 1 && s % (uint32_t)e->timing_every != (uint32_t)e->timing_every / 2;
+    for (int h = 0; h < P.n; ++h) {
+        const Parts::Part& p = P.part[h];
+        const noise_t* nz = ring.at(s, p.g0);
+        if (s == 0) {
+            if (int rc = timed(e, K_SELECT, p.t.G, [&] {
+                    return launch_select(p.t, p.roots, p.active, nz, S.prm, p.st);
+                }, p.st))
+                return rc;
+        } else if (int rc = timed(e, K_BACKUP_SELECT, p.t.G, [&] {
+                       return launch_backup_select(p.t, p.roots, p.active, p.pol, p.val, nz, S.prm, p.st);
+                   }, p.st)) {
+            return rc;
+        }
+        if (!p.t.need) {
+            if (int rc = evaluate(e, p.t.leaf_state, p.t.G, p.pol, p.val, p.st)) return rc;
+            continue;
+        }
+        // row loads clamped to the part's own rows (the next part's compaction writes its rows on another stream)
+        const TileMap tm{p.t.bcnt, buckets_of(p.t.G), (int32_t)p.t.G};
+        if (int rc = timed(e, K_COMPACT, p.t.G, [&] { return launch_eval_compact(p.t, p.st); }, p.st)) return rc;
+        if (int rc = evaluate(e, p.t.cstate, p.t.G, p.pol, p.val, p.st, &tm)) return rc;
+    }
+    return 0;
+}
+
+// The search chunk by chunk of the root-noise ring (one chunk = e->noise_chunk simulations, with or without
+// noise): per chunk one k_search_grp launch (grp), or its simulation steps over the game parts. Ends with the
+// last simulation's expand/backup per part and the parts' streams joined into the engine stream.
+static int run_chunks(oaz_engine* e, const Search& S, bool grp) {
+    const Parts P(e, S, grp ? 1 : game_parts(e, S.t.G));
+    const NoiseRing ring{e, S, P, e->noise_chunk};
+    const uint32_t nchunks = (S.sims + ring.chunk - 1) / ring.chunk;
+    e->times.parts = (uint64_t)P.n;
+    if (int rc = ring.produce(0)) return rc;
+    if (int rc = P.fork()) return rc;
+    bool spent = false;
+    for (uint32_t c = 0; c < nchunks && !spent; ++c) {
+        if (int rc = ring.produce(c + 1)) return rc;
+        if (int rc = ring.wait(c)) return rc;
+        if (grp) {
+            if (int rc = grp_chunk(e, S, ring, c)) return rc;
+        } else {
+            for (uint32_t s = c * ring.chunk, s1 = std::min(s + ring.chunk, S.sims); s < s1 && !spent; ++s)
+                if (int rc = sim_step(e, S, P, ring, s, &spent)) return rc;
+        }
+        if (int rc = ring.release(c)) return rc;
+    }
+    e->timing_skip = false;
+    for (int h = 0; h < P.n; ++h) {
+        const Parts::Part& p = P.part[h];
+        if (int rc = timed(e, K_EXPAND, p.t.G, [&] {
+                return launch_expand_backup(p.t, p.roots, p.active, p.pol, p.val, p.st);
+            }, p.st))
+            return rc;
+    }
+    return P.join();
+}
+
+// The simulations of one move on the path that fits (search_path). On an error the game parts' streams are
+// joined into the engine stream anyway (all of them, whatever the number of parts was: the drivers' early
+// returns skip the join), so oaz_sync and buffer reuse after an error wait for them.
+static int run_sims(oaz_engine* e, const TreeView& t, const oaz_state* roots, const uint8_t* active,
+                    const uint64_t* gids, const uint32_t* plies) {
+    const bool budget = e->cfg.search_time_ns > 0, noise = e->cfg.train_noise && e->noise;
+    const SearchPath path = search_path(e, t.G, noise);
+    const NNView w = nn_view(e, nullptr);
+    Search S{t, roots, active, gids, plies, search_params(e), (uint32_t)e->cfg.sims, noise,
+             e->cfg.evaluator == OAZ_EVAL_HASH ? nullptr : &w, budget ? e->deadline.get() : nullptr,
+             budget ? e->sims_run.get() : nullptr};
+    if (!compact_leaves(e, t.G)) {  // (always so on the one-launch paths) rows = game ids
+        S.t.need = nullptr;
+        S.t.slot = nullptr;
+    }
+    e->last = LastSearch{t.G};
+    int rc = path == PATH_STEPS ? 0 : arm_device_budget(e, t.G);
+    if (!rc) rc = path == PATH_LAT ? search_lat(e, S) : run_chunks(e, S, path == PATH_GRP);
+    if (rc) {
+        const std::string msg = g_err;
+        for (int h = 1; h < kMaxParts; ++h)
+            if (hipEventRecord(e->ev_part[h], e->stream3[h - 1]) == hipSuccess)
+                (void)hipStreamWaitEvent(e->stream, e->ev_part[h], 0);
+        e->timing_skip = false;
+        g_err = msg;
+    }
+    return rc;
 }
 
 static int reduce_stats(oaz_engine* e, uint32_t G, uint64_t out[GS_COUNT]) {
@@ -1114,7 +1120,8 @@ static int search_core(oaz_engine* e, const oaz_state* roots, int G) {
     e->search_calls++;
     HIP_TRY(launch_tree_reset(t, e->stream));
     if (int rc = run_sims(e, t, e->s_roots, nullptr, nullptr, e->s_ply)) return rc;
-    return timed(e, 3, (uint32_t)G, [&] { return launch_search_finalize(t, e->s_roots, e->s_move, e->s_pi, e->stream); });
+    return timed(e, K_FINALIZE, (uint32_t)G,
+                 [&] { return launch_search_finalize(t, e->s_roots, e->s_move, e->s_pi, e->stream); });
 }
 
 // Engine internals used by the arena (oaz_arena.hip, declared in oaz_host.h).
@@ -1200,7 +1207,7 @@ extern "C" int oaz_selfplay_step(oaz_engine* e, int moves) {
         if (int rc = begin_budget(e)) return rc;
         HIP_TRY(launch_tree_reset(t, e->stream));  // a fresh tree per move (the last ply's stays dumpable)
         if (int rc = run_sims(e, t, e->root, e->active, e->game_id, e->ply)) return rc;
-        if (int rc = timed(e, 3, e->G, [&] { return launch_selfplay_move(t, sv, e->stream); })) return rc;
+        if (int rc = timed(e, K_FINALIZE, e->G, [&] { return launch_selfplay_move(t, sv, e->stream); })) return rc;
     }
     return 0;
 }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of the C3 bench (short, no baselines/PMC) over environment settings of the A/B build:
-# ENVS="OAZ_TREE_FUSE=0 OAZ_TREE_FUSE=1" ROUNDS=3 tools/bench_ab.sh  -> value and ms_per_step per run
+# ENVS="OAZ_TREE_SEG=0 OAZ_TREE_SEG=1" ROUNDS=3 tools/bench_ab.sh  -> value and ms_per_step per run
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
 mkdir -p gpurun_out/bench_ab
 export OAZ_LIB=$PWD/onitama-alphazero_amd/onitama_az/libonitama_az_ab.so
