@@ -43,7 +43,7 @@ OAZ_HD constexpr uint32_t sq_bit(int sq) { return 0x80000000u >> sq; }
 // centred pattern by the square delta and masking wrapped files by (delta % 5). Here every
 // pattern square is turned into a (dr, dc) offset from the centre and applied to `from`
 // when it stays on the board — the same set (the file masks remove exactly the column
-// wrap-arounds; tests/test_rules_host.py checks the tables against the oracle).
+// wrap-arounds; tests/test_host.py::test_attack_maps_equal_oracle checks the tables against the oracle).
 struct AttackTable {
     uint32_t m[2][16][25];
 };
@@ -218,56 +218,8 @@ OAZ_HD double u01(uint32_t a, uint32_t b) {
 // IEEE +, -, *, / and explicit fused multiply-adds (correctly rounded on the host, x86 vfmadd / libm fma,
 // and on the device, v_fma_f64) with no compiler contraction, so the device, the host (oaz_root_noise)
 // and the C oracle compute bit-identical draws.
-//
-// OAZ_NOISE_F32 (the A/B build only, a measured option): the previous f32 draw (one 32-bit word per
-// uniform, polynomials in f32), which resolves the law's ends only to f32.
-#ifndef OAZ_NOISE_F32
-#define OAZ_NOISE_F32 0
-#endif
-#if OAZ_NOISE_F32
-typedef float noise_t;
-#else
-typedef double noise_t;
-#endif
-
-OAZ_HD float nz_u(uint32_t x) {  // uniform in (0,1): (2k + 1) 2^-24, k = x >> 9 (exact in f32)
-    return (float)(((x >> 9) << 1) | 1u) * (1.0f / 16777216.0f);
-}
-OAZ_HD float nz_log(float x) {  // natural log for normal x > 0 (|rel err| < 2e-7)
-    uint32_t b = __builtin_bit_cast(uint32_t, x);
-    int e = (int)((b >> 23) & 0xFF) - 127;
-    b = (b & 0x007FFFFFu) | 0x3F800000u;  // mantissa m in [1, 2)
-    float m = __builtin_bit_cast(float, b);
-    if (m > 1.41421356f) {
-        m = m * 0.5f;
-        e += 1;
-    }
-    const float t = (m - 1.0f) / (m + 1.0f), t2 = t * t;
-    const float p = t * (2.0f + t2 * (0.666666667f + t2 * (0.4f + t2 * (0.285714286f + t2 * 0.222222222f))));
-    return (float)e * 0.693147182f + p;
-}
-OAZ_HD float nz_exp(float x) {  // e^x (|rel err| < 3e-7); 0 below -87, +inf above 88
-    if (x < -87.0f) return 0.0f;
-    if (x > 88.0f) return __builtin_bit_cast(float, 0x7F800000u);
-    const float k = (float)(int)(x * 1.44269504f + (x >= 0.0f ? 0.5f : -0.5f));
-    const float r = (x - k * 0.693145752f) - k * 1.42860677e-6f;  // ln2 split hi + lo
-    const float q = 1.0f + r * (1.0f + r * (0.5f + r * (0.166666667f + r * (0.0416666667f + r * (0.00833333333f +
-                                                                                        r * 0.00138888889f)))));
-    return q * __builtin_bit_cast(float, (uint32_t)((int)k + 127) << 23);
-}
-// f32 draw (OAZ_NOISE_F32): idx (2j + {0: running best, 1: child j}) of comparison j; c2 = ply << 16 | sim.
-// Attempt t takes Philox block (game lo, game hi, c2, idx << 12 | t), words 0, 1 and then 2, 3.
-OAZ_HD float root_noise_f32(uint64_t seed, uint64_t game, uint32_t c2, uint32_t idx, float alpha, int K) {
-    const float ia = 1.0f / alpha, ib = 1.0f / (alpha * (float)(K - 1));
-    for (uint32_t t = 0; t < 1024u; ++t) {
-        const u32x4 r = philox(seed, (uint32_t)game, (uint32_t)(game >> 32), c2, (idx << 12) | t);
-        const float lx = nz_log(nz_u(r.x)) * ia, ly = nz_log(nz_u(r.y)) * ib;
-        if (nz_exp(lx) + nz_exp(ly) <= 1.0f) return 1.0f / (1.0f + nz_exp(ly - lx));
-        const float lx2 = nz_log(nz_u(r.z)) * ia, ly2 = nz_log(nz_u(r.w)) * ib;
-        if (nz_exp(lx2) + nz_exp(ly2) <= 1.0f) return 1.0f / (1.0f + nz_exp(ly2 - lx2));
-    }
-    return 1.0f / (float)K;  // (never reached: 2048 rejections in a row)
-}
+// (The f32 draw this replaced is gone; its A/B is profiles/r06b_noise_f64_vs_f32_ab.log.)
+typedef double noise_t;  // one draw, as the engine's noise ring stores it
 
 // ln 2 split: kLn2Hi has 21 trailing zero bits (k * kLn2Hi is exact for |k| < 2^21), kLn2Lo the rest.
 constexpr double kLn2Hi = 6.93147180369123816490e-01, kLn2Lo = 1.90821492927058770002e-10;
@@ -339,13 +291,9 @@ OAZ_HD double root_noise_f64(uint64_t seed, uint64_t game, uint32_t c2, uint32_t
     }
     return 1.0 / (double)K;  // (never reached: 2048 rejections in a row)
 }
-// The engine's draw (k_root_noise, oaz_root_noise): f64, or f32 in an OAZ_NOISE_F32 build.
+// The engine's draw (k_root_noise, oaz_root_noise).
 OAZ_HD noise_t root_noise(uint64_t seed, uint64_t game, uint32_t c2, uint32_t idx, double alpha, int K) {
-#if OAZ_NOISE_F32
-    return root_noise_f32(seed, game, c2, idx, (float)alpha, K);
-#else
     return root_noise_f64(seed, game, c2, idx, alpha, K);
-#endif
 }
 
 // Deck::default (deck.rs:139-151): random 5 of the 16 cards; Fisher-Yates driven by

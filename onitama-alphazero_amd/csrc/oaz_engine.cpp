@@ -287,7 +287,7 @@ struct oaz_engine {
     Stream stream2;                      // root-noise producer, overlaps the NN kernel
     Stream stream3[kMaxParts - 1];       // the streams of game parts 1.. (oaz_config.parts)
     int cus = 256;                      // compute units of the device (leaf-compaction threshold)
-    DevBuf<noise_t> noise;               // [2][noise_chunk][G][kNoiseStride] (f64 draws; f32 in an OAZ_NOISE_F32 build)
+    DevBuf<noise_t> noise;               // [2][noise_chunk][G][kNoiseStride] (f64 draws)
     uint32_t noise_chunk = 16;           // simulations per noise ring slot (noise_chunk_for)
     uint32_t G = 0, cap = 0, pathcap = 0, hcap = 0, out_cap = 0;
     int32_t sims_cap = 0;                // cfg.sims at creation: trees and paths are sized for it

@@ -732,15 +732,9 @@ __device__ __forceinline__ void root_noise_pairs(const TreeView& t, const noise_
         const int j = 16 * c + sl;
         const uint32_t off =
             go && j >= 1 && j < K ? (g * (uint32_t)kNoiseStride + 2u * (uint32_t)j) * kB : 0x80000000u;
-#if OAZ_NOISE_F32
-        const auto d = __builtin_amdgcn_raw_buffer_load_b64(nr, (int)off, 0, 0);
-        na[c] = __uint_as_float(d[0]);
-        nb[c] = __uint_as_float(d[1]);
-#else
         const auto d = __builtin_amdgcn_raw_buffer_load_b128(nr, (int)off, 0, 0);
         na[c] = __builtin_bit_cast(double, ((uint64_t)d[1] << 32) | d[0]);
         nb[c] = __builtin_bit_cast(double, ((uint64_t)d[3] << 32) | d[2]);
-#endif
     }
 }
 
@@ -988,16 +982,12 @@ __device__ __forceinline__ void select_seg_body(const TreeView& t, const oaz_sta
     }
 }
 
-#ifndef OAZ_WG_FOLD
-#define OAZ_WG_FOLD 1  // the workgroup's root noise folds on one wave (WgFold); 0: per segment (A/B build)
-#endif
 // register budget: 64 VGPRs = 8 waves/SIMD, no spill (the fold operands 40 KB: four workgroups per CU)
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OAZ_TREE_WPE)))
 k_select_seg(TreeView t, const oaz_state* __restrict__ roots, const uint8_t* __restrict__ active,
              const noise_t* __restrict__ noise, SearchParams prm) {
     __shared__ WgFold wf;
-    select_seg_body<NodesGlobalRegs, OAZ_WG_FOLD>(t, roots, active, noise, prm, seg_game(), nullptr, NodesGlobalRegs{},
-                                                  &wf);
+    select_seg_body<NodesGlobalRegs, true>(t, roots, active, noise, prm, seg_game(), nullptr, NodesGlobalRegs{}, &wf);
 }
 
 template <int N>
@@ -1190,8 +1180,8 @@ k_backup_select_seg(TreeView t, const oaz_state* __restrict__ roots, const uint8
     expand_backup_seg_body(t, roots, active, policy, value, g, lds.spol[threadIdx.x >> 4], NodesGlobalRegs{});
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    select_seg_body<NodesGlobalRegs, OAZ_WG_FOLD, true>(t, roots, active, noise, prm, g, nullptr, NodesGlobalRegs{},
-                                                        &lds.wf);
+    select_seg_body<NodesGlobalRegs, true, true>(t, roots, active, noise, prm, g, nullptr, NodesGlobalRegs{},
+                                                 &lds.wf);
 }
 
 // calculate_priors (mcts_arena.rs:104-124) + best child (87-94) for every root.

@@ -78,7 +78,7 @@ constexpr int kRowB = 128;                     // LDS row of one piece plane: 64
 constexpr int kPlaneB = nn::kSB * 25 * kRowB;  // 51,200 B per piece plane
 constexpr int kImageB = 2 * kPlaneB;           // 102,400 B
 constexpr int kLdsFloats = kImageB / 4 + nn::kWaves * nn::kScratch;  // 26,624 floats = 106,496 B
-// first layer on fp16 MFMA (k_nn_h3, TR; weights: nnl::l1c): K block 0 = bitboard taps 0-7 of plane
+// first layer on fp16 MFMA (k_nn_h3; weights: nnl::l1c): K block 0 = bitboard taps 0-7 of plane
 // q = lane >> 4 (square-independent), K block 1 per square = tap 8 of plane q, then the 17 constant planes'
 // table T[square]. The 0/1 B operands are built in-kernel (lut: LDS table of the 8-tap bit patterns).
 constexpr int kLutB = 256 * 16;                       // 256 patterns x f16x8
@@ -93,6 +93,13 @@ __device__ __forceinline__ int nbr_index(int sq, int t) {
     // square sq (row-major 5x5) shifted by tap t = (dy, dx) in {-1,0,1}^2; 25 = off board
     const int r = sq / 5 + t / 3 - 1, c = sq % 5 + t % 3 - 1;
     return (r >= 0 && r < 5 && c >= 0 && c < 5) ? r * 5 + c : 25;
+}
+
+// The constant first-layer planes of a position (common.rs:26-80): the mover's two cards and its colour.
+__device__ __forceinline__ int mover_info(const oaz_state st) {
+    const int blue = st.to_move & 1;
+    const int c0 = (blue ? st.cards[2] : st.cards[0]) & 15, c1 = (blue ? st.cards[3] : st.cards[1]) & 15;
+    return c0 | (c1 << 4) | (blue << 8);
 }
 
 __device__ __forceinline__ float wave_sum_f(float v) {
@@ -451,12 +458,7 @@ __global__ void __launch_bounds__(64 * nn::kWaves) k_nn_sq16(const oaz_state* __
         const int b = min(b0 + pos, sp.cap - 1);  // an empty tile of a bucket starts past cap
         const uint32_t* w = reinterpret_cast<const uint32_t*>(&states[b]);
         const uint32_t bb = kq == 0 ? w[2] : kq == 1 ? w[0] : kq == 2 ? w[3] : w[1];
-        if (tid < nn::kSB) {
-            const oaz_state st = states[b];
-            const int blue = st.to_move & 1;
-            const int c0 = (blue ? st.cards[2] : st.cards[0]) & 15, c1 = (blue ? st.cards[3] : st.cards[1]) & 15;
-            pinfo[tid] = c0 | (c1 << 4) | (blue << 8);
-        }
+        if (tid < nn::kSB) pinfo[tid] = mover_info(states[b]);
         if (b0 >= B) return;  // an empty tile of a compacted bucket (uniform over the workgroup)
         __syncthreads();
         f32x4 acc[nn::kTPW];
@@ -563,12 +565,6 @@ constexpr int8_t kSqOrderU[25] = {6, 7, 8, 11, 12, 13, 16, 17, 18, 0, 4, 20, 24,
 #ifndef OAZ_H3_KH
 #define OAZ_H3_KH 4  // squares per batch (A fragments in flight per step run)
 #endif
-#ifndef OAZ_H1_PP
-#define OAZ_H1_PP 1  // bf16 mode: two image buffers, the convs alternate (one barrier per conv)
-#endif
-#ifndef OAZ_H1_L1F16
-#define OAZ_H1_L1F16 1  // bf16 mode: the first layer on fp16 MFMA (the fp16x3 mode's), not exact fp32 MFMA
-#endif
 #ifndef OAZ_H1_SPLIT
 #define OAZ_H1_SPLIT 13
 #endif
@@ -601,62 +597,26 @@ constexpr TapList tap_list(int grp, int t) {
     return L;
 }
 
-// Batch plan: the 18 (tap, K-half) steps cut into near-equal batches of <= KH on-board squares.
-struct X6Batch {
-    int t, m, n;
-    int8_t j[16], nb[16];
-};
-struct X6Plan {
-    int nbat;
-    X6Batch b[96];
-};
-constexpr X6Plan x6_plan(int grp, int kh) {
-    X6Plan P{};
-    for (int s = 0; s < 18; ++s) {
-        const TapList L = tap_list(grp, s / 2);
-        const int nb = (L.n + kh - 1) / kh;
-        int q = 0;
-        for (int k = 0; k < nb; ++k) {
-            const int n = (L.n - q) / (nb - k);  // near-equal split, larger batches last
-            X6Batch B{};
-            B.t = s / 2;
-            B.m = s % 2;
-            B.n = n;
-            for (int i = 0; i < n; ++i) {
-                B.j[i] = L.j[q + i];
-                B.nb[i] = L.nb[q + i];
-            }
-            q += n;
-            P.b[P.nbat++] = B;
-        }
-    }
-    return P;
-}
-template <int GRP, int KH>
-struct X6PlanOf {
-    static constexpr X6Plan P = x6_plan(GRP, KH);
-};
-
-// k_nn_h3 plan: the 18 (tap, K-half) steps of the group cut into batches of <= KH squares. first:
-// the batch starts a step run (its B pieces were prefetched); nstep: the step of the next run (its B
-// pieces are prefetched now).
-struct H3Batch {
+// Batch plan of a split kernel's conv: the 18 (tap, K-half) steps of the group cut into near-equal
+// batches of <= KH on-board squares. first: the batch starts a step run (its B pieces were prefetched);
+// nstep: the step of the next run (its B pieces are prefetched now), -1 after the last.
+struct ConvBatch {
     int t, m, n, first, nstep;
     int8_t j[16], nb[16];
 };
-struct H3Plan {
+struct ConvPlan {
     int nbat;
-    H3Batch b[96];
+    ConvBatch b[96];
 };
-constexpr H3Plan h3_plan(int grp, int kh) {
-    H3Plan P{};
+constexpr ConvPlan conv_plan(int grp, int kh) {
+    ConvPlan P{};
     for (int s = 0; s < 18; ++s) {  // step = tap * 2 + K-half
         const TapList L = tap_list(grp, s / 2);
         const int nb = (L.n + kh - 1) / kh;
         int q = 0;
         for (int k = 0; k < nb; ++k) {
             const int m = (L.n - q) / (nb - k);  // near-equal split, larger batches last
-            H3Batch B{};
+            ConvBatch B{};
             B.t = s / 2;
             B.m = s % 2;
             B.n = m;
@@ -679,32 +639,30 @@ constexpr H3Plan h3_plan(int grp, int kh) {
     return P;
 }
 template <int GRP, int KH>
-struct H3PlanOf {
-    static constexpr H3Plan P = h3_plan(GRP, KH);
+struct ConvPlanOf {
+    static constexpr ConvPlan P = conv_plan(GRP, KH);
 };
 
 // Kernel configurations (8 waves: two per SIMD, square groups GRP0 / GRP1 x 4 N-tiles, <= 256 VGPRs;
-// KH: squares per batch of A fragments). DBG (diagnostic builds only, `make AB=1`; timing only, wrong
-// results): 2 per-wave s_memtime phase sums written over the first policy rows (tools/nn_phases.py),
-// 3 no conv A reads, 4 no conv B loads, 7 conv B loads of one step, 9 conv A reads discarded (ablations),
-// 5 workgroup start / end stamps
-// (tools/nn_timeline.py).
-template <int DBG_ = 0>
+// KH: squares per batch of A fragments). DBG (diagnostic builds of k_nn_h3 / k_nn_h3s only, `make AB=1`;
+// timing only, wrong results): 2 per-wave s_memtime phase sums written over the first policy rows
+// (tools/nn_phases.py), 3 no conv A reads, 4 no conv B loads, 7 conv B loads of one step, 9 conv A reads
+// discarded (ablations), 5 workgroup start / end stamps (tools/nn_timeline.py).
 struct X6Cfg {  // k_nn_x6 (OAZ_FP32_SPLIT, and k_nn_h3's fp16-range recompute): 15 / 10 squares
-    static constexpr int WAVES = 8, KH = OAZ_H3_KH, NS = 15, GRP0 = 3, GRP1 = 4, TR = 0, DBG = DBG_;
+    static constexpr int WAVES = 8, KH = OAZ_H3_KH, NS = 15, GRP0 = 3, GRP1 = 4;
 };
 template <int BF_, int DBG_ = 0>
 struct H3Cfg {  // k_nn_h3: 17 / 8 squares (bf16: 13 / 12); BF: OAZ_BF16 mode (one bf16 piece, one product; C5)
     static constexpr int kSplit = BF_ ? kH1Split : kH3Split;
     static constexpr int WAVES = 8, KH = OAZ_H3_KH, NS = kSplit > 12 ? kSplit : 25 - kSplit, GRP0 = BF_ ? 9 : 7,
-                         GRP1 = BF_ ? 10 : 8, TR = 1, BF = BF_, DBG = DBG_;
+                         GRP1 = BF_ ? 10 : 8, BF = BF_, DBG = DBG_;
 };
 
 // A-fragment loads / MFMAs of batch K (compile-time: the LDS address is one of six per-lane bases
 // ab[m][seg] = lo[m] + seg * 64 KiB plus an immediate offset < 64 KiB)
 template <int GRP, int KH, int K, int N>
 __device__ __forceinline__ void x6_load(bf16x8 (&a)[N], const char* img, const int (&ab)[2][3], int piece) {
-    constexpr X6Batch B = X6PlanOf<GRP, KH>::P.b[K];
+    constexpr ConvBatch B = ConvPlanOf<GRP, KH>::P.b[K];
 #pragma unroll
     for (int q = 0; q < N; ++q)
         if (q < B.n) {
@@ -715,42 +673,39 @@ __device__ __forceinline__ void x6_load(bf16x8 (&a)[N], const char* img, const i
 
 template <int GRP, int KH, int K, int NS, int N>
 __device__ __forceinline__ void x6_mfma(f32x4 (&acc)[NS], const bf16x8 (&a)[N], const bf16x8& bv) {
-    constexpr X6Batch B = X6PlanOf<GRP, KH>::P.b[K];
+    constexpr ConvBatch B = ConvPlanOf<GRP, KH>::P.b[K];
 #pragma unroll
     for (int q = 0; q < N; ++q)
         if (q < B.n) acc[B.j[q]] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[q], bv, acc[B.j[q]], 0, 0, 0);
 }
 
-// B pieces of (tap, K-half) step S for N-tile nt: [step][piece][N-tile][lane] bf16x8, read with
-// buffer loads (descriptor + one per-lane VGPR offset + a constant SGPR offset: no 64-bit vector
-// address arithmetic per load)
-struct X6W {
+// Packed MFMA weight fragments [entry][N-tile][lane] x 16 B (`floats` floats at p), read by N-tile nt's
+// lane with buffer loads (descriptor + one per-lane VGPR offset + a constant SGPR offset: no 64-bit
+// vector address arithmetic per load). A conv's B pieces: entry = [step][piece], step = (tap, K-half).
+struct FragW {
     __amdgpu_buffer_rsrc_t r;
     int voff;  // (nt * 64 + lane) * 16
 };
-__device__ __forceinline__ X6W x6_w(const float* p, int lane, int nt) {
-    X6W w;
-    w.r = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)(nnl::kConvW<OAZ_FP32_SPLIT> * 4), 0x00020000);
+__device__ __forceinline__ FragW frag_w(const float* p, size_t floats, int lane, int nt) {
+    FragW w;
+    w.r = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)(floats * 4), 0x00020000);
     w.voff = (nt * 64 + lane) * 16;
     return w;
 }
-__device__ __forceinline__ bf16x8 x6_ldb(const X6W& w, int entry) {  // entry = (step * 3 + piece) * 4
+__device__ __forceinline__ bf16x8 x6_ldb(const FragW& w, int entry) {  // entry = (step * 3 + piece) * 4
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w.r, w.voff, entry * 64 * 16, 0));
 }
 
 template <class C, int GRP, int K>
-__device__ __forceinline__ void x6_step_b(const X6W& W, bf16x8 (&b)[3], bf16x8 (&bn)[3]) {
-    constexpr const X6Plan& P = X6PlanOf<GRP, C::KH>::P;
-    constexpr X6Batch B = P.b[K];
-    constexpr int step = B.t * 2 + B.m;
-    constexpr bool first_of_step = K == 0 || P.b[K - 1].t * 2 + P.b[K - 1].m != step;
-    if constexpr (first_of_step && K > 0) {
+__device__ __forceinline__ void x6_step_b(const FragW& W, bf16x8 (&b)[3], bf16x8 (&bn)[3]) {
+    constexpr ConvBatch B = ConvPlanOf<GRP, C::KH>::P.b[K];
+    if constexpr (B.first && K > 0) {
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) b[pc] = bn[pc];
     }
-    if constexpr (first_of_step && step + 1 < 18) {  // prefetch the next step's B pieces
+    if constexpr (B.first && B.nstep >= 0) {  // prefetch the next step run's B pieces
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc) bn[pc] = x6_ldb(W, ((step + 1) * 3 + pc) * 4);
+        for (int pc = 0; pc < 3; ++pc) bn[pc] = x6_ldb(W, (B.nstep * 3 + pc) * 4);
     }
 }
 
@@ -758,7 +713,7 @@ __device__ __forceinline__ void x6_step_b(const X6W& W, bf16x8 (&b)[3], bf16x8 (
 // with K's parity):
 //   load Y = h | m*Bh, m*Bm | load X = l | h*Bh, h*Bm, h*Bl | load Y = next m | l*Bh
 template <class C, int GRP, int K>
-__device__ __forceinline__ void conv_x6_batch(f32x4 (&acc)[C::NS], const char* img, const X6W& W,
+__device__ __forceinline__ void conv_x6_batch(f32x4 (&acc)[C::NS], const char* img, const FragW& W,
                                               bf16x8 (&b)[3], bf16x8 (&bn)[3], bf16x8 (&X)[C::KH],
                                               bf16x8 (&Y)[C::KH], const int (&ab)[2][3]) {
     constexpr int KH = C::KH, NS = C::NS;
@@ -770,13 +725,13 @@ __device__ __forceinline__ void conv_x6_batch(f32x4 (&acc)[C::NS], const char* i
     x6_mfma<GRP, KH, K, NS>(acc, Y, b[0]);  // hh
     x6_mfma<GRP, KH, K, NS>(acc, Y, b[1]);  // hm
     x6_mfma<GRP, KH, K, NS>(acc, Y, b[2]);  // hl
-    if constexpr (K + 1 < X6PlanOf<GRP, KH>::P.nbat) x6_load<GRP, KH, K + 1>(Y, img, ab, 1);
+    if constexpr (K + 1 < ConvPlanOf<GRP, KH>::P.nbat) x6_load<GRP, KH, K + 1>(Y, img, ab, 1);
     x6_mfma<GRP, KH, K, NS>(acc, X, b[0]);  // lh
     __builtin_amdgcn_sched_barrier(0);      // bound the live ranges: no loads hoisted across batches
 }
 
 template <class C, int GRP, int... K>
-__device__ __forceinline__ void conv_x6_run(f32x4 (&acc)[C::NS], const char* img, const X6W& W, const int (&lo)[2],
+__device__ __forceinline__ void conv_x6_run(f32x4 (&acc)[C::NS], const char* img, const FragW& W, const int (&lo)[2],
                                             std::integer_sequence<int, K...>) {
     int ab[2][3];
 #pragma unroll
@@ -903,8 +858,7 @@ __device__ __forceinline__ void first_layer_x6(f32x4 (&acc)[C::NS], const L1Regs
             const int r = sq / 5 + t / 3 - 1, c = sq % 5 + t % 3 - 1;
             if (r >= 0 && r < 5 && c >= 0 && c < 5) {
                 const float a = (float)((bb >> (31 - (r * 5 + c))) & 1u);
-                acc[j] = C::TR ? __builtin_amdgcn_mfma_f32_16x16x4f32(R.w[t], a, acc[j], 0, 0, 0)
-                               : __builtin_amdgcn_mfma_f32_16x16x4f32(a, R.w[t], acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, R.w[t], acc[j], 0, 0, 0);
             }
         }
     const int c0 = cinfo & 15, c1 = (cinfo >> 4) & 15, blue = (cinfo >> 8) & 1;
@@ -921,9 +875,7 @@ __device__ __forceinline__ void first_layer_x6(f32x4 (&acc)[C::NS], const L1Regs
 #pragma unroll
             for (int q = 0; q < kBatch; ++q)
                 if (j0 + q < grp_n(GRP))
-                    acc[j0 + q] = C::TR
-                                      ? __builtin_amdgcn_mfma_f32_16x16x4f32(tb[q][st], a[st], acc[j0 + q], 0, 0, 0)
-                                      : __builtin_amdgcn_mfma_f32_16x16x4f32(a[st], tb[q][st], acc[j0 + q], 0, 0, 0);
+                    acc[j0 + q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[st], tb[q][st], acc[j0 + q], 0, 0, 0);
         if (j0 + kBatch < grp_n(GRP)) fetch(j0 + kBatch);
     }
 }
@@ -949,27 +901,13 @@ __device__ __forceinline__ void nn_x6_body(const oaz_state* __restrict__ states,
 
     f32x4 acc[NS];
     f32x4 skip[NS];
-    uint64_t ph[6] = {0, 0, 0, 0, 0, 0};  // DBG 2: first layer, conv, barrier 1, epilogue, barrier 2, heads
-    uint64_t tm = C::DBG == 2 ? __builtin_amdgcn_s_memtime() : 0;
-    auto stamp = [&](int k) {
-        if constexpr (C::DBG == 2) {
-            const uint64_t t = __builtin_amdgcn_s_memtime();
-            ph[k] += t - tm;
-            tm = t;
-        }
-    };
     {  // encoder + first layer
         L1Regs<GRP> l1;
         first_layer_x6_fetch<GRP>(l1, blob + nnl::kL1B, lane, nt);
         const int b = min(b0 + i, sp.cap - 1);  // an empty tile of a bucket starts past cap
         const uint32_t* w = reinterpret_cast<const uint32_t*>(&states[b]);
         const uint32_t bb = kq == 0 ? w[2] : kq == 1 ? w[0] : kq == 2 ? w[3] : w[1];
-        if (tid < nn::kSB) {
-            const oaz_state st = states[b];
-            const int blue = st.to_move & 1;
-            const int c0 = (blue ? st.cards[2] : st.cards[0]) & 15, c1 = (blue ? st.cards[3] : st.cards[1]) & 15;
-            pinfo[tid] = c0 | (c1 << 4) | (blue << 8);
-        }
+        if (tid < nn::kSB) pinfo[tid] = mover_info(states[b]);
         if (b0 >= B) return;  // an empty tile of a compacted bucket (uniform over the workgroup)
         __syncthreads();
 #pragma unroll
@@ -980,25 +918,19 @@ __device__ __forceinline__ void nn_x6_body(const oaz_state* __restrict__ states,
     }
     // 2 * blocks convs through one call site (small block 1: conv + BN + ReLU; small block 2:
     // conv + BN, + skip, ReLU)
-    stamp(0);
     const float* p = OAZ_NN_CONVS_AT(blob);
     for (int c = 0; c < 2 * blocks; ++c) {
 #pragma unroll
         for (int j = 0; j < NS; ++j) acc[j] = f32x4{};
-        conv_x6_run<C, GRP>(acc, img, x6_w(p, lane, nt), lo,
-                            std::make_integer_sequence<int, X6PlanOf<GRP, C::KH>::P.nbat>{});
-        stamp(1);
+        conv_x6_run<C, GRP>(acc, img, frag_w(p, nnl::kConvW<OAZ_FP32_SPLIT>, lane, nt), lo,
+                            std::make_integer_sequence<int, ConvPlanOf<GRP, C::KH>::P.nbat>{});
         p += nnl::kConvW<OAZ_FP32_SPLIT>;
         uint32_t pk[NS][2][3];
         epilogue_x6_pack<C, GRP>(acc, pk, p, skip, co, c & 1, c & 1);
-        stamp(3);
         __syncthreads();
-        stamp(2);
         epilogue_x6_store<C, GRP>(pk, img, eo);
-        stamp(3);
         p += nnl::kConvTail<OAZ_FP32_SPLIT>;
         __syncthreads();
-        stamp(4);
     }
     // heads: the value / policy 1x1 convs as split-fp32 MFMAs on the LDS image (one 16x16 tile
     // per square: rows = positions, columns 0 / 1 / 2 = value, policy planes 0 / 1), then the MLPs
@@ -1056,11 +988,6 @@ __device__ __forceinline__ void nn_x6_body(const oaz_state* __restrict__ states,
         }
         heads_mlp<NP>(fq, bq, p, lane, B, policy, value);
     }
-    if constexpr (C::DBG == 2) {
-        stamp(5);
-        __syncthreads();
-        if (lane < 6 && b0 + nn::kSB <= B) policy[(size_t)b0 * 50 + wave * 6 + lane] = (float)ph[lane];
-    }
 }
 
 template <class C>
@@ -1093,14 +1020,11 @@ __global__ void __launch_bounds__(64 * C::WAVES) k_nn_x6(const oaz_state* __rest
 // [piece][row][64 channels] (row = square*16 + position, 128 B); the 16-byte chunk c of row r sits
 // at c ^ key(r), an XOR-linear key on the row bits found by exhaustive search
 // (tools/h3_swizzle.py): conflict-free A-fragment ds_read_b128s and epilogue ds_write_b32s.
-// PF: the B pieces of each conv's first step run are requested during the previous phase's
-// epilogue (h3_first_b); same-box A/B -0.6 % (fp16x3) / -1.4 % (bf16 6-block) per launch. The
-// phase-stamp build (DBG 2) keeps the old order: with both, its stamps make the allocator spill.
-#ifndef OAZ_H3_PF
-#define OAZ_H3_PF 1
-#endif
+// The B pieces of each conv's first step run are requested during the previous phase's epilogue
+// (h3_first_b); same-box A/B -0.6 % (fp16x3) / -1.4 % (bf16 6-block) per launch. The phase-stamp build
+// (DBG 2) fetches them at the conv's start: with both, its stamps make the allocator spill.
 template <class C>
-constexpr bool h3_pf() { return OAZ_H3_PF && C::DBG != 2; }
+constexpr bool h3_pf() { return C::DBG != 2; }
 namespace h3 {
 __device__ __forceinline__ int key(int r) {
     return ((r & 1) << 1) ^ ((r >> 1) & 1) ^ (((r >> 2) & 1) << 2) ^ (((r >> 3) & 1) << 1);
@@ -1114,14 +1038,14 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 template <class C, int GRP>
-using H3P = H3PlanOf<GRP, C::KH>;
+using H3P = ConvPlanOf<GRP, C::KH>;
 
 // A-fragment loads / MFMAs of batch K; the LDS address is one of four per-lane bases
 // ab[m][seg] = lo[m] + seg * 64 KiB plus an immediate offset < 64 KiB (piece 1 = + kPlaneB)
 template <class C, int GRP, int K, int N>
 __device__ __forceinline__ void h3_load(f16x8 (&a)[N], const char* img, const int (&ab)[2][2], int piece) {
     if constexpr (C::DBG == 3 && K > 1) return;  // ablation (timing only, wrong results): no A reads
-    constexpr H3Batch B = H3P<C, GRP>::P.b[K];
+    constexpr ConvBatch B = H3P<C, GRP>::P.b[K];
 #pragma unroll
     for (int q = 0; q < N; ++q)
         if (q < B.n) {
@@ -1139,7 +1063,7 @@ __device__ __forceinline__ void h3_load(f16x8 (&a)[N], const char* img, const in
 // of 16x16x32 are symmetric, so the same registers serve either order.
 template <class C, int GRP, int K, int N>
 __device__ __forceinline__ void h3_mfma(f32x4 (&acc)[C::NS], const f16x8 (&a)[N], const f16x8& bv) {
-    constexpr H3Batch B = H3P<C, GRP>::P.b[K];
+    constexpr ConvBatch B = H3P<C, GRP>::P.b[K];
 #pragma unroll
     for (int q = 0; q < N; ++q)
         if (q < B.n)
@@ -1149,21 +1073,14 @@ __device__ __forceinline__ void h3_mfma(f32x4 (&acc)[C::NS], const f16x8 (&a)[N]
                                 : __builtin_amdgcn_mfma_f32_16x16x32_f16(bv, a[q], acc[B.j[q]], 0, 0, 0);
 }
 
-// B pieces of (tap, K-half) step S for N-tile nt: [step][piece][N-tile][lane] f16x8, buffer loads
-__device__ __forceinline__ X6W h3_w(const float* p, int lane, int nt, int bytes = (int)(nnl::kConvW<OAZ_FP32_SPLIT16> * 4)) {
-    X6W w;
-    w.r = __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, bytes, 0x00020000);
-    w.voff = (nt * 64 + lane) * 16;
-    return w;
-}
-__device__ __forceinline__ f16x8 h3_ldb(const X6W& w, int entry) {  // entry = (step * 2 + piece) * 4
+__device__ __forceinline__ f16x8 h3_ldb(const FragW& w, int entry) {  // entry = (step * 2 + piece) * 4
     return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(w.r, w.voff, entry * 64 * 16, 0));
 }
 
 // B pieces: b = the current step run's, bn = the next run's (loaded one step run ahead)
 template <class C, int GRP, int K>
-__device__ __forceinline__ void h3_step_b(const X6W& W, f16x8 (&b)[2], f16x8 (&bn)[2]) {
-    constexpr H3Batch B = H3P<C, GRP>::P.b[K];
+__device__ __forceinline__ void h3_step_b(const FragW& W, f16x8 (&b)[2], f16x8 (&bn)[2]) {
+    constexpr ConvBatch B = H3P<C, GRP>::P.b[K];
     if constexpr (B.first && K > 0) {
         b[0] = bn[0];
         b[1] = bn[1];
@@ -1183,7 +1100,7 @@ __device__ __forceinline__ void h3_step_b(const X6W& W, f16x8 (&b)[2], f16x8 (&b
 // BF batch K: one piece, one product; the next batch's fragments load during this one's MFMAs
 // (two buffers, roles swap with K's parity)
 template <class C, int GRP, int K>
-__device__ __forceinline__ void conv_h1_batch(f32x4 (&acc)[C::NS], const char* img, const X6W& W, f16x8 (&b)[2],
+__device__ __forceinline__ void conv_h1_batch(f32x4 (&acc)[C::NS], const char* img, const FragW& W, f16x8 (&b)[2],
                                               f16x8 (&bn)[2], f16x8 (&X)[C::KH], f16x8 (&Xn)[C::KH],
                                               const int (&ab)[2][2]) {
     h3_step_b<C, GRP, K>(W, b, bn);
@@ -1195,7 +1112,7 @@ __device__ __forceinline__ void conv_h1_batch(f32x4 (&acc)[C::NS], const char* i
 // fp16x3 batch K (X holds its lo pieces on entry and the next batch's on exit):
 //   load Y = hi | lo*Bhi | load X = next lo | hi*Bhi, hi*Blo
 template <class C, int GRP, int K>
-__device__ __forceinline__ void conv_h3_batch(f32x4 (&acc)[C::NS], const char* img, const X6W& W, f16x8 (&b)[2],
+__device__ __forceinline__ void conv_h3_batch(f32x4 (&acc)[C::NS], const char* img, const FragW& W, f16x8 (&b)[2],
                                               f16x8 (&bn)[2], f16x8 (&X)[C::KH], f16x8 (&Y)[C::KH],
                                               const int (&ab)[2][2]) {
     h3_step_b<C, GRP, K>(W, b, bn);
@@ -1210,8 +1127,8 @@ __device__ __forceinline__ void conv_h3_batch(f32x4 (&acc)[C::NS], const char* i
 // The B pieces of a conv's first step run, requested before the previous phase's epilogue and
 // barriers (their L2 latency would otherwise stall both waves of the SIMD at every conv's start).
 template <class C, int GRP>
-__device__ __forceinline__ void h3_first_b(f16x8 (&b)[2], const X6W& W) {
-    constexpr H3Batch B0 = H3P<C, GRP>::P.b[0];
+__device__ __forceinline__ void h3_first_b(f16x8 (&b)[2], const FragW& W) {
+    constexpr ConvBatch B0 = H3P<C, GRP>::P.b[0];
     if constexpr (C::BF) {
         b[0] = h3_ldb(W, (B0.t * 2 + B0.m) * 4);
         b[1] = b[0];
@@ -1222,7 +1139,7 @@ __device__ __forceinline__ void h3_first_b(f16x8 (&b)[2], const X6W& W) {
 }
 
 template <class C, int GRP, int... K>
-__device__ __forceinline__ void conv_h3_run(f32x4 (&acc)[C::NS], const char* img, const X6W& W, const int (&lo)[2],
+__device__ __forceinline__ void conv_h3_run(f32x4 (&acc)[C::NS], const char* img, const FragW& W, const int (&lo)[2],
                                             const f16x8 (&bfirst)[2], std::integer_sequence<int, K...>) {
     int ab[2][2];
 #pragma unroll
@@ -1289,6 +1206,18 @@ __device__ __forceinline__ void h3t_pack_one(const f32x4& acc, uint32_t (&pk)[2]
         }
     }
 }
+// The fp16 range guard: hmax = the largest hi bit patterns a lane has split (two u16 halves). Both hi pairs
+// of a square in one v_pk_maximum3_f16 (IEEE maximum: an overflowed hi is +inf = 0x7C00, a NaN stays NaN;
+// hi >= +0 after ReLU).
+__device__ __forceinline__ void h3_track(uint32_t& hmax, const uint32_t (&pk)[2][2]) {
+    hmax = __builtin_bit_cast(
+        uint32_t, __builtin_elementwise_maximum(
+                      __builtin_elementwise_maximum(__builtin_bit_cast(f16x2, hmax), __builtin_bit_cast(f16x2, pk[0][0])),
+                      __builtin_bit_cast(f16x2, pk[0][1])));
+}
+__device__ __forceinline__ bool h3_overflowed(uint32_t hmax) {  // an fp16 hi term is inf (or NaN)
+    return (hmax & 0xffffu) >= 0x7C00u || (hmax >> 16) >= 0x7C00u;
+}
 template <class C, int GRP, bool FIRST, int RES>
 __device__ __forceinline__ void epilogue_h3t_pack(const f32x4 (&acc)[C::NS], uint32_t (&pk)[C::NS][2][2],
                                                   const f32x4& bb, const f32x4& sc, f32x4 (&skip)[C::NS],
@@ -1296,13 +1225,7 @@ __device__ __forceinline__ void epilogue_h3t_pack(const f32x4 (&acc)[C::NS], uin
 #pragma unroll
     for (int j = 0; j < grp_n(GRP); ++j) {
         h3t_pack_one<FIRST, (bool)C::BF, RES>(acc[j], pk[j], bb, sc, skip[j]);
-        // the range guard: both hi pairs of the square in one v_pk_maximum3_f16 (IEEE maximum: an
-        // overflowed hi is +inf = 0x7C00, a NaN stays NaN; hi >= +0 after ReLU)
-        if constexpr (!C::BF)
-            hmax = __builtin_bit_cast(
-                uint32_t, __builtin_elementwise_maximum(
-                              __builtin_elementwise_maximum(__builtin_bit_cast(f16x2, hmax), __builtin_bit_cast(f16x2, pk[j][0][0])),
-                              __builtin_bit_cast(f16x2, pk[j][0][1])));
+        if constexpr (!C::BF) h3_track(hmax, pk[j]);
     }
 }
 template <class C, int GRP>
@@ -1316,7 +1239,7 @@ __device__ __forceinline__ void epilogue_h3t_store(const uint32_t (&pk)[C::NS][2
 }
 
 // The whole forward for the waves of square group GRP.
-// k_nn_h3 (TR) first layer, all on fp16 MFMA (conv_init_1, net.rs:16-27 / 119-131): for output square
+// k_nn_h3 first layer, all on fp16 MFMA (conv_init_1, net.rs:16-27 / 119-131): for output square
 // sq the K dimension is (plane q, tap t) of the 4 bitboard planes and the 17 constant planes (the
 // mover's two cards and the colour plane, common.rs:26-80, summed over sq's on-board taps on the
 // host: T[sq]). Block 0 = taps 0-7 of plane q (k = 8q + t), block 1 = tap 8 of plane q (k = 32 + 8q)
@@ -1397,12 +1320,8 @@ struct L1H {  // the first layer's A operands (K block 0, and K block 1 of each 
 // issued at kernel start, so the loads overlap the state load, the LUT build and the barrier
 template <int GRP>
 __device__ __forceinline__ void first_layer_h3f_fetch(L1H<GRP>& R, const float* l1c, int lane, int nt) {
-    X6W A;
-    A.r = __builtin_amdgcn_make_buffer_rsrc((void*)l1c, (short)0, (int)(nnl::kL1cInv * 4), 0x00020000);
-    A.voff = (nt * 64 + lane) * 16;
-    auto ld = [&](int blk, int pc) {  // [blk][pc][nt][lane]
-        return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(A.r, A.voff, (blk * 2 + pc) * 4 * 64 * 16, 0));
-    };
+    const FragW A = frag_w(l1c, nnl::kL1cInv, lane, nt);
+    auto ld = [&](int blk, int pc) { return h3_ldb(A, (blk * 2 + pc) * 4); };  // [blk][pc][nt][lane]
     R.a0h = ld(0, 0);
     R.a0l = ld(0, 1);
     constexpr L1Slots S = L1SlotsOf<GRP>::S;
@@ -1526,8 +1445,8 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
     const int nt = wave & 3;
     const int b0 = sp.b0;
     constexpr int kPrec = C::BF ? OAZ_BF16 : OAZ_FP32_SPLIT16;  // the blob's layout
-    // (bf16 mode with two image buffers: one piece plane each, so the image area is kImageB as well)
-    int* pinfo = reinterpret_cast<int*>(lds + (C::BF && !OAZ_H1_PP ? h3::kPlaneB : h3::kImageB) / 4);
+    // (bf16 mode: two image buffers of one piece plane each, so the image area is kImageB as well)
+    int* pinfo = reinterpret_cast<int*>(lds + h3::kImageB / 4);
     const int i = lane & 15, kq = lane >> 4;
     const int lo[2] = {h3::chunk_off(i, kq), h3::chunk_off(i, 4 + kq)};
     const int cq = nt * 16 + 4 * kq;  // this lane's 4 channels cq .. cq + 3 of position i
@@ -1536,7 +1455,7 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
     f32x4 acc[NS];
     f32x4 skip[NS];
     f16x8 bpre[2];  // the next conv's first B pieces (h3_first_b)
-    uint32_t hmax = 0;  // largest hi bit patterns (two u16 halves)
+    uint32_t hmax = 0;  // the fp16 range guard (h3_track)
     // DBG 2: first layer (MFMA tail + epilogue), conv, barrier 1, epilogue, barrier 2, heads, kernel start (state,
     // LUT, barrier), first-layer MFMAs (incl. their operand loads)
     uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1549,10 +1468,8 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         }
     };
     {  // encoder + first layer
-        L1Regs<GRP> l1;
         L1H<GRP> l1h;
         // the fp16 first layer's fragments and inverse scales (after the heads; bf16 mode: same section)
-        constexpr bool kF16 = !C::BF || OAZ_H1_L1F16;
         const float* l1c = OAZ_NN_L1C_AT(blob, kPrec, blocks);
         // the state loads first: vmcnt retires in issue order, so the pinfo / LUT work before the
         // barrier then waits for these and not for the first-layer operands issued after them
@@ -1561,28 +1478,21 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         const uint32_t bb = kq == 0 ? w[2] : kq == 1 ? w[0] : kq == 2 ? w[3] : w[1];
         oaz_state st{};
         if (tid < nn::kSB) st = states[b];
-        if constexpr (kF16)
-            first_layer_h3f_fetch<GRP>(l1h, l1c, lane, nt);
-        else
-            first_layer_x6_fetch<GRP>(l1, blob + nnl::kL1B, lane, nt);
-        if (tid < nn::kSB) {
+        first_layer_h3f_fetch<GRP>(l1h, l1c, lane, nt);
+        if (tid < nn::kSB) {  // mover_info(st) written out: the call changes this kernel's register allocation
             const int blue = st.to_move & 1;
             const int c0 = (blue ? st.cards[2] : st.cards[0]) & 15, c1 = (blue ? st.cards[3] : st.cards[1]) & 15;
             pinfo[tid] = c0 | (c1 << 4) | (blue << 8);
         }
-        if constexpr (kF16)
-            for (int t = tid; t < 512; t += 64 * C::WAVES) l1_lut_build(img + h3::kLutOff, t);
+        for (int t = tid; t < 512; t += 64 * C::WAVES) l1_lut_build(img + h3::kLutOff, t);
         const f32x4 bias1t = *reinterpret_cast<const f32x4*>(blob + nnl::kL1Bias + cq);
         if (b0 >= B) return false;  // an empty tile of a compacted bucket (uniform over the workgroup)
         __syncthreads();
         stamp(6);
 #pragma unroll
         for (int j = 0; j < NS; ++j) acc[j] = skip[j] = f32x4{};
-        if constexpr (kF16)  // fp16 MFMA on the 0/1 inputs
-            first_layer_h3f<C, GRP>(acc, l1h, bb, pinfo[i], lane, reinterpret_cast<const char*>(lds),
-                                    std::make_integer_sequence<int, grp_n(GRP)>{});
-        else  // exact fp32 MFMA on the 0/1 inputs, as k_nn_x6
-            first_layer_x6<C, GRP>(acc, l1, blob + nnl::kL1Table, bb, pinfo[i], lane, nt);
+        first_layer_h3f<C, GRP>(acc, l1h, bb, pinfo[i], lane, reinterpret_cast<const char*>(lds),
+                                std::make_integer_sequence<int, grp_n(GRP)>{});  // fp16 MFMA on the 0/1 inputs
         if constexpr (C::DBG == 2) {  // the MFMA results, so the stamp follows the MFMAs
             float z = 0.0f;
 #pragma unroll
@@ -1591,12 +1501,11 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         }
         stamp(7);
         uint32_t pk[NS][2][2];
-        const f32x4 inv1 = !kF16 ? f32x4{1.0f, 1.0f, 1.0f, 1.0f}
-                                 : *reinterpret_cast<const f32x4*>(l1c + nnl::kL1cInv + cq);
+        const f32x4 inv1 = *reinterpret_cast<const f32x4*>(l1c + nnl::kL1cInv + cq);
         epilogue_h3t_pack<C, GRP, true, 0>(acc, pk, bias1t, inv1, skip, hmax);
         if constexpr (h3_pf<C>()) {
             constexpr size_t kWc = nnl::kConvW<kPrec>;
-            h3_first_b<C, GRP>(bpre, h3_w(OAZ_NN_CONVS_AT(blob), lane, nt, (int)(kWc * 4)));
+            h3_first_b<C, GRP>(bpre, frag_w(OAZ_NN_CONVS_AT(blob), kWc, lane, nt));
         }
         epilogue_h3t_store<C, GRP>(pk, img, eot);
         __syncthreads();
@@ -1616,10 +1525,10 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         // reads 1 and writes 0 (the first layer and the heads use buffer 0). Every wave has finished
         // reading the buffer a conv writes before the previous conv's closing barrier, so the
         // in-place barrier between the MFMAs and the stores is not needed.
-        constexpr bool kPP = C::BF && OAZ_H1_PP;
+        constexpr bool kPP = C::BF;
         char* const rd = kPP && RES == 1 ? img + h3::kPlaneB : img;
         char* const wr = kPP && RES == 0 ? img + h3::kPlaneB : img;
-        conv_h3_run<C, GRP>(acc, rd, h3_w(p, lane, nt, (int)(kWc * 4)), lo, bpre,
+        conv_h3_run<C, GRP>(acc, rd, frag_w(p, kWc, lane, nt), lo, bpre,
                             std::make_integer_sequence<int, H3P<C, GRP>::P.nbat>{});
         stamp(1);
         const float* pc = p;
@@ -1627,7 +1536,7 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         uint32_t pk[NS][2][2];
         epilogue_h3t_pack<C, GRP, false, RES>(acc, pk, bbt, sct, skip, hmax);  // before the barrier: a
         // (unconditional, so that the old pieces are dead during the conv; the last conv reloads its own)
-        if constexpr (h3_pf<C>()) h3_first_b<C, GRP>(bpre, h3_w(more ? p : pc, lane, nt, (int)(kWc * 4)));
+        if constexpr (h3_pf<C>()) h3_first_b<C, GRP>(bpre, frag_w(more ? p : pc, kWc, lane, nt));
         stamp(3);                                                             // wave done early packs
         if constexpr (!kPP) __syncthreads();                                  // beside its partner's MFMAs
         stamp(2);
@@ -1650,7 +1559,7 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
         if (lane < 8 && b0 + nn::kSB <= B) policy[(size_t)b0 * 50 + wave * 8 + lane] = v;
     }
     if constexpr (C::BF) return false;  // bf16 pieces have fp32's exponent range
-    return (hmax & 0xffffu) >= 0x7C00u || (hmax >> 16) >= 0x7C00u;  // hi = inf
+    return h3_overflowed(hmax);
 }
 
 // fp16-range fallback: a workgroup in which any lane split an activation beyond the fp16 range
@@ -1663,11 +1572,8 @@ __device__ __forceinline__ bool nn_h3_body(const oaz_state* __restrict__ states,
 template <class C>
 struct H3Fallback {
     static constexpr bool kOn = !C::BF && C::DBG == 0;
-    using X = X6Cfg<>;
-    // bf16 mode keeps two buffers of one piece plane (+ the position info): 103 KB, and 168 VGPRs, so
-    // two tree-kernel waves (80 VGPRs, 15.6 KB per workgroup) fit beside the two NN waves of a SIMD
-    static constexpr int kBase = C::BF && !OAZ_H1_L1F16 ? (OAZ_H1_PP ? h3::kImageB : h3::kPlaneB) / 4 + 256
-                                                        : h3::kLdsFloats + h3::kLutB / 4;
+    using X = X6Cfg;
+    static constexpr int kBase = h3::kLdsFloats + h3::kLutB / 4;  // the image, the head scratch, the first layer's LUT
     static constexpr int kLds = kOn && x6::kLdsFloats > kBase ? x6::kLdsFloats : kBase;
 };
 
@@ -1861,19 +1767,13 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
     const float* p = OAZ_NN_CONVS_AT(blob);  // the first conv's packed weights
     const float* ph0 = OAZ_NN_HEADS_AT(blob, OAZ_FP32_SPLIT16, blocks);  // the head parameters
     uint32_t hmax = 0;
-    auto track = [&](const uint32_t (&pk)[2][2]) {  // the fp16 range guard (hi >= +0 after ReLU)
-        hmax = __builtin_bit_cast(
-            uint32_t, __builtin_elementwise_maximum(
-                          __builtin_elementwise_maximum(__builtin_bit_cast(f16x2, hmax), __builtin_bit_cast(f16x2, pk[0][0])),
-                          __builtin_bit_cast(f16x2, pk[0][1])));
-    };
     auto store2 = [&](char* img, int eo, const uint32_t (&pk)[2][2]) {
         *reinterpret_cast<uint2*>(img + eo) = uint2{pk[0][0], pk[0][1]};
         *reinterpret_cast<uint2*>(img + h3s::kPlaneB + eo) = uint2{pk[1][0], pk[1][1]};
     };
     H3sW R;  // compute waves: the current conv's B pieces
     if (compute) {
-        const X6W W0 = h3_w(p, lane, nt);
+        const FragW W0 = frag_w(p, nnl::kConvW<OAZ_FP32_SPLIT16>, lane, nt);
 #pragma unroll
         for (int st = 0; st < 18; ++st) {  // the first conv's pieces, in flight during the first layer
             R.w[st][0] = h3_ldb(W0, (st * 2 + 0) * 4);
@@ -1898,13 +1798,8 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
             bias1t = *reinterpret_cast<const f32x4*>(res.l1 + h3s::kL1Bytes + cq * 4);
             inv1 = *reinterpret_cast<const f32x4*>(res.l1 + h3s::kL1Bytes + 256 + cq * 4);
         } else {
-            X6W A;
-            A.r = __builtin_amdgcn_make_buffer_rsrc((void*)l1c, (short)0, (int)(nnl::kL1cInv * 4), 0x00020000);
-            A.voff = (nt * 64 + lane) * 16;
-            auto ld = [&](int blk, int pc) {  // [blk][pc][nt][lane]
-                return __builtin_bit_cast(
-                    f16x8, __builtin_amdgcn_raw_buffer_load_b128(A.r, A.voff, (blk * 2 + pc) * 4 * 64 * 16, 0));
-            };
+            const FragW A = frag_w(l1c, nnl::kL1cInv, lane, nt);
+            auto ld = [&](int blk, int pc) { return h3_ldb(A, (blk * 2 + pc) * 4); };  // [blk][pc][nt][lane]
             a0h = ld(0, 0);
             a0l = ld(0, 1);
 #pragma unroll
@@ -1953,11 +1848,11 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
         uint32_t pk[2][2];
         f32x4 r0 = {}, r1 = {};
         h3t_pack_one<true, false, 0>(acc0, pk, bias1t, inv1, r0);
-        track(pk);
+        h3_track(hmax, pk);
         store2(img0, eo0, pk);
         h3t_pack_one<true, false, 0>(acc1, pk, bias1t, inv1, r1);
         if (live1) {
-            track(pk);
+            h3_track(hmax, pk);
             store2(img0, eo1, pk);
         }
         skipx[(nt * 64 + lane) * 2 + 0] = r0;  // the first block's residual, for the compute waves
@@ -1984,7 +1879,7 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
             constexpr size_t kWc = nnl::kConvW<OAZ_FP32_SPLIT16>;
             const f32x4 bbt = *reinterpret_cast<const f32x4*>(p + kWc + nnl::kConvBias + cq);
             const f32x4 sct = *reinterpret_cast<const f32x4*>(p + kWc + nnl::kConvInv + cq);
-            const X6W Wn = h3_w(p + nnl::kConvStride<OAZ_FP32_SPLIT16>, lane, nt);
+            const FragW Wn = frag_w(p + nnl::kConvStride<OAZ_FP32_SPLIT16>, kWc, lane, nt);
             f32x4 acc0 = {}, acc1 = {};
             f16x8 xl0[2], xh0[2], xl1[2], xh1[2];
             {
@@ -2020,11 +1915,11 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
             stamp(2);
             uint32_t pk[2][2];
             h3t_pack_one<false, false, RES>(acc0, pk, bbt, sct, skip0);
-            track(pk);
+            h3_track(hmax, pk);
             store2(wr, eo0, pk);
             h3t_pack_one<false, false, RES>(acc1, pk, bbt, sct, skip1);
             if (live1) {
-                track(pk);
+                h3_track(hmax, pk);
                 store2(wr, eo1, pk);
             }
         }
@@ -2088,7 +1983,7 @@ __device__ __forceinline__ bool nn_h3s_body(const oaz_state* __restrict__ states
         for (int k = 0; k < 6; ++k) v = lane == k ? (float)ph[k] : v;
         if (lane < 6) policy[(size_t)b * 50 + wave * 6 + lane] = v;
     }
-    return (hmax & 0xffffu) >= 0x7C00u || (hmax >> 16) >= 0x7C00u;  // an fp16 hi term overflowed
+    return h3_overflowed(hmax);
 }
 
 // The one-launch search's resident operands (H3sResident): all threads of the workgroup, then a barrier.
@@ -2180,7 +2075,7 @@ hipError_t launch_nn_forward(const NNView& w, const oaz_state* s, int B, float* 
                            w.tm);
     } else if (w.precision == OAZ_FP32_SPLIT) {
         // 8 waves, uneven 15 / 10 square split, pipelined batches of <= 4 squares
-        hipLaunchKernelGGL(k_nn_x6<X6Cfg<>>, dim3(grid), block, 0, st, s, B, w.blob, w.blocks, policy, value, w.tm);
+        hipLaunchKernelGGL(k_nn_x6<X6Cfg>, dim3(grid), block, 0, st, s, B, w.blob, w.blocks, policy, value, w.tm);
     } else if (w.precision == OAZ_BF16) {
         // the k_nn_h3 structure with one bf16 piece and one product, convs in pairs
         hipLaunchKernelGGL(k_nn_h3<H3Cfg<1>>, dim3(grid), block, 0, st, s, B, w.blob, w.blocks, policy, value, nullptr,
