@@ -529,6 +529,48 @@ int oaz_pure_mcts_search(const oaz_state* roots, int G, const oaz_pure_mcts_conf
  * device's kept buffer (OAZ_ERR_STATE while a search uses it). */
 int oaz_pure_mcts_release_workspace(int device);
 
+/* One search per root, each root with its own Mcts{..}: the parameter sweep of bin/mcts_parameter_check.rs (every
+ * pairing's games, both sides) as one launch per ply, and the agent's search_time clock. */
+typedef struct oaz_pure_mcts_root {      /* 24 bytes: one root's Mcts{..} (ai/mcts/mod.rs:13-30) */
+    int32_t  max_playouts;               /* >= 0 */
+    int32_t  min_node_visits;            /* >= 0 */
+    float    exploration_c;
+    uint32_t reserved;                   /* 0 */
+    uint64_t stream;                     /* the rollout generator's game word: Philox(seed; stream, playout, 0x9C7A0000, d/4); < 2^32 */
+} oaz_pure_mcts_root;
+
+typedef struct oaz_pure_mcts_each_config { /* 32 bytes: what the roots of a call share */
+    uint64_t seed;
+    int64_t  search_time_ns;             /* 0 = off: exactly max_playouts playouts per root */
+    int32_t  rollout_cap;                /* as oaz_pure_mcts_config.rollout_cap */
+    int32_t  device;
+    int32_t  reserved[2];
+} oaz_pure_mcts_each_config;
+
+/* Root g's tree capacity = oaz_pure_mcts_tree_capacity of its (max_playouts, min_node_visits) (0 for a negative
+ * one). offsets (optional, G + 1) = their exclusive prefix sums. Returns the total. Host only. */
+size_t oaz_pure_mcts_each_capacity(const oaz_pure_mcts_root* par, int G, size_t* offsets);
+/* Root g's tree, move and value are those of oaz_pure_mcts_search on that root alone with par[g]'s max_playouts,
+ * min_node_visits and exploration_c, the call's seed and rollout_cap, and game_id0 = par[g].stream. A UCT value
+ * that is NaN (0 * inf: exploration_c = 0 and an unvisited child) is ordered as the x86 default NaN 0xFFC00000,
+ * the smallest key of f32::total_cmp, which is what the reference's arithmetic gives.
+ * search_time_ns > 0 is the reference's loop condition (mcts_arena.rs:56-62) read on the device: a root takes the
+ * device's constant-rate clock when its search starts, and playout p (0-based) starts only while p < max_playouts
+ * and, for p >= min(max_playouts, min_node_visits + 2), while the clock is below the start + search_time_ns.
+ * (Defined here: the first min_node_visits + 2 playouts always run, so the root is expanded; the reference
+ * panics when its clock cuts earlier.) The clock is read once per playout and nothing waits on it.
+ * out_playouts[g] (optional) = the playouts root g ran; its tree is that of a search with max_playouts =
+ * out_playouts[g]. tree_out (optional) receives root g's nodes at tree_out + tree_offsets[g], at most
+ * tree_offsets[g + 1] - tree_offsets[g] of them; oaz_pure_mcts_each_capacity gives the offsets that hold every
+ * tree, and device memory is their total. Every argument is checked before a device is touched (OAZ_ERR_ARG, the
+ * message naming the root); G == 0 returns OAZ_OK with zeroed statistics. Device, stream and workspace as
+ * oaz_pure_mcts_search. */
+int oaz_pure_mcts_search_each(const oaz_state* roots, const oaz_pure_mcts_root* par, int G,
+                              const oaz_pure_mcts_each_config* cfg, oaz_move* out_move, float* out_value,
+                              int32_t* out_playouts /* optional: playouts each root ran */,
+                              oaz_pure_mcts_stats* stats, oaz_pure_node* tree_out /* optional, packed */,
+                              const size_t* tree_offsets /* G + 1, required with tree_out */);
+
 /* ---- alpha-beta agent (the fourth opponent of Evaluator::pit, evaluator.rs:276-312) --------------
  * The reference's `AlphaBeta` agent (onitama-game/src/ai/alpha_beta/mod.rs:35-183): fail-soft alpha-beta
  * without move ordering or a table, Red maximising and Blue minimising Evaluation::evaluate
@@ -536,7 +578,8 @@ int oaz_pure_mcts_release_workspace(int device);
  * current card's moves. generate_move (mod.rs:136-170) deepens iteratively, depth = 1 .. max_depth - 1,
  * and keeps only the last iteration's result, so a run the clock does not cut equals one search to
  * max_depth - 1 plies: that search runs here, one GPU wave per root with one lane per root move.
- * search_time is not enforced (as the pure-MCTS agent's). */
+ * search_time is not enforced by this entry point: oaz_alphabeta_generate_move has the clock (as
+ * oaz_pure_mcts_search_each has the pure-MCTS agent's). */
 typedef struct oaz_alphabeta_config {
     int32_t max_depth;   /* 6 (alpha_beta/mod.rs:24); the arena's opponent uses 4 (evaluator.rs:303-306).
                             Accepted: 2..6 (the reference panics below 2, mod.rs:161) */

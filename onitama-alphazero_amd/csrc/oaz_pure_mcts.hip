@@ -306,6 +306,192 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OAZ_PM_WPE))
     st[7] = 0;
 }
 
+// k_pure_mcts with the search's parameters per lane (oaz_pure_mcts_search_each): root g searches with par[g]'s
+// playouts, min_node_visits and c on par[g]'s rollout stream, in its own slice [tree_off[g], tree_off[g + 1]) of
+// the packed trees. The playout is k_pure_mcts's, statement for statement, but for two things:
+//  - a UCT value that is NaN (0 * inf at c = 0 for an unvisited child) is ordered as the x86 default NaN
+//    0xFFC00000, the smallest key of f32::total_cmp, whatever sign the GPU's multiplier gives it: that is the
+//    value the reference's and the oracle's arithmetic produce;
+//  - with the clock on, playout po >= floor starts only while the device's constant-rate clock is below the
+//    lane's deadline (mcts_arena.rs:56-62: `while now.elapsed() < search_time && playouts < max_playouts`); the
+//    first floor = min(playouts, min_visits + 2) playouts always run, so the root is expanded when it can be.
+// A wave runs as long as its longest lane. Occupancy is not what bounds a launch of a few thousand roots, so
+// the kernel takes the registers it needs to stay out of scratch memory.
+struct EachParams {
+    int rollout_cap, clock_on;
+    uint64_t seed, ticks;
+};
+
+constexpr int32_t kNanKey = (int32_t)0x803FFFFFu;  // total_key of 0xFFC00000
+
+#ifndef OAZ_PM_EACH_WPE
+#define OAZ_PM_EACH_WPE 5
+#endif
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(OAZ_PM_EACH_WPE))) void k_pure_mcts_each(
+    const oaz_state* roots, const oaz_pure_mcts_root* par, const uint64_t* tree_off, int G, EachParams p,
+    const float* ln_tab, oaz_pure_node* nodes, oaz_move* out_move, float* out_value, int32_t* out_playouts,
+    uint64_t* stats /* [G][8] */) {
+    __shared__ uint32_t att_s[2][16][25];
+    for (int i = threadIdx.x; i < 2 * 16 * 25; i += blockDim.x) (&att_s[0][0][0])[i] = (&c_att.m[0][0][0])[i];
+    __syncthreads();
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    oaz_pure_node* T = nodes + tree_off[g];
+    const uint32_t cap = (uint32_t)(tree_off[g + 1] - tree_off[g]);
+    const int playouts = par[g].max_playouts, min_visits = par[g].min_node_visits;
+    const float c = par[g].exploration_c;
+    const uint32_t stream = (uint32_t)par[g].stream;
+    const int floor_po = min_visits >= playouts - 2 ? playouts : min_visits + 2;
+    const uint64_t deadline = p.clock_on ? (uint64_t)wall_clock64() + p.ticks : 0;
+    const int root_color = roots[g].to_move & 1;
+    T[0] = oaz_pure_node{0u, 0.0f, 0.0f, 0u, 0xFFFFFFFFu, 0, 0, 0};
+    uint32_t n_nodes = 1;
+    __shared__ uint64_t stl[5][64];
+    uint64_t& st_plies = stl[0][threadIdx.x];
+    uint64_t& st_pass = stl[1][threadIdx.x];
+    uint64_t& st_exp = stl[2][threadIdx.x];
+    uint64_t& st_capped = stl[3][threadIdx.x];
+    uint64_t& st_over = stl[4][threadIdx.x];
+    st_plies = st_pass = st_exp = st_capped = st_over = 0;
+    int po = 0;
+    for (; po < playouts; ++po) {
+        if (p.clock_on && po >= floor_po && (uint64_t)wall_clock64() >= deadline) break;
+        oaz_state s = roots[g];
+        uint32_t idx = 0;
+        // 1. selection
+        while ((T[idx].flags & kExpanded) && !(T[idx].flags & kTerminal) && T[idx].nch) {
+            const float lnN = ln_tab[T[idx].visits];
+            const uint32_t first = T[idx].first, nch = T[idx].nch;
+            uint32_t best = first;
+            int32_t bk = INT32_MIN;
+            for (uint32_t c0 = 0; c0 < nch; c0 += kSelBatch) {
+                uint32_t vis[kSelBatch];
+                float wr[kSelBatch];
+#pragma unroll
+                for (int j = 0; j < kSelBatch; ++j)
+                    if (c0 + j < nch) {
+                        vis[j] = T[first + c0 + j].visits;
+                        wr[j] = T[first + c0 + j].winrate;
+                    }
+#pragma unroll
+                for (int j = 0; j < kSelBatch; ++j)
+                    if (c0 + j < nch) {
+                        const float u = wr[j] + c * sqrtf(lnN / (float)vis[j]);
+                        const int32_t k = u != u ? kNanKey : total_key(u);
+                        if (k >= bk) {  // max_by: the last maximum wins
+                            bk = k;
+                            best = first + c0 + j;
+                        }
+                    }
+            }
+            const uint32_t m = T[best].mv;
+            const int color = s.to_move & 1;
+            const int res = make_move_regs(s, mv_from(m), mv_to(m), mv_piece(m), mv_slot(m), color);
+            s.to_move ^= 1;
+            if (is_win(res)) T[best].flags |= kTerminal;
+            idx = best;
+        }
+        // 2. expansion
+        if (!(T[idx].flags & (kExpanded | kTerminal)) && T[idx].visits > (uint32_t)min_visits) {
+            const int color = s.to_move & 1;
+            const int n = movegen_kth(s, color, att_s[color], -1, nullptr);
+            if (n_nodes + (uint32_t)n <= cap) {
+                T[idx].first = n_nodes;
+                T[idx].nch = (uint8_t)n;
+                for (int k = 0; k < n; ++k) {
+                    uint32_t m = 0;
+                    movegen_kth(s, color, att_s[color], k, &m);
+                    T[n_nodes + k] = oaz_pure_node{0u, 0.0f, 0.0f, 0u, idx, (uint16_t)m, 0, 0};
+                }
+                n_nodes += n;
+                T[idx].flags |= kExpanded;
+                ++st_exp;
+            } else {
+                ++st_over;  // capacity reached: the node stays a leaf
+            }
+        }
+        // 3. simulation; reward colour = the colour that moved into idx
+        const int reward_color = idx == 0 ? root_color : ((s.to_move & 1) ^ 1);
+        Rng rng{p.seed, stream, (uint32_t)po, 0u, {}};
+        int mr = current_state(s);
+        float r;
+        if (is_win(mr)) {
+            r = reward_f(mr, reward_color);
+        } else {
+            int color = s.to_move & 1, plies = 0;
+            bool capped = false;
+            while (!is_win(mr)) {
+                if (plies >= p.rollout_cap) {
+                    capped = true;
+                    break;
+                }
+                uint32_t m = 0;
+                const int n = rollout_pick(s, color, att_s[color], rng, &m);
+                if (n == 0) {  // pass with a random own card (state.rs:139-142)
+                    state_rotate(s, (color ? 2 : 0) + (int)rng.below(2));
+                    color ^= 1;
+                    ++st_pass;
+                    ++plies;
+                    continue;
+                }
+                mr = make_move_regs(s, mv_from(m), mv_to(m), mv_piece(m), mv_slot(m), color);
+                color ^= 1;
+                ++plies;
+            }
+            st_plies += plies;
+            if (capped) {
+                ++st_capped;
+                r = 0.0f;
+            } else {
+                r = reward_f(mr, reward_color);
+            }
+        }
+        // 4. backpropagation
+        for (uint32_t v = idx;;) {
+            T[v].visits += 1;
+            T[v].reward += r;
+            T[v].winrate = T[v].reward / (float)T[v].visits;
+            if (v == 0) break;
+            v = T[v].parent;
+            r = -r;
+        }
+    }
+    // best root child by visits, last maximum (mcts_arena.rs:64-79)
+    oaz_move mv;
+    float value = 0.0f;
+    if (T[0].nch == 0) {
+        mv.from = 25;
+        mv.to = 25;
+        mv.piece = 0;
+        mv.slot = (uint8_t)(root_color ? 2 : 0);
+    } else {
+        uint32_t best = T[0].first, bv = 0;
+        for (uint32_t ch = T[0].first; ch < T[0].first + T[0].nch; ++ch)
+            if (T[ch].visits >= bv) {
+                bv = T[ch].visits;
+                best = ch;
+            }
+        const uint32_t m = T[best].mv;
+        mv.from = (uint8_t)mv_from(m);
+        mv.to = (uint8_t)mv_to(m);
+        mv.piece = (uint8_t)mv_piece(m);
+        mv.slot = (uint8_t)mv_slot(m);
+        value = T[best].winrate;
+    }
+    out_move[g] = mv;
+    out_value[g] = value;
+    out_playouts[g] = po;
+    uint64_t* st = stats + (size_t)g * 8;
+    st[0] = (uint64_t)po;
+    st[1] = st_exp;
+    st[2] = st_plies;
+    st[3] = st_pass;
+    st[4] = st_capped;
+    st[5] = n_nodes;
+    st[6] = st_over;
+    st[7] = 0;
+}
+
 }  // namespace pm
 
 extern "C" void oaz_pure_mcts_config_default(oaz_pure_mcts_config* c) {  // ai/mcts/mod.rs:21-30
@@ -456,6 +642,143 @@ extern "C" int oaz_pure_mcts_search(const oaz_state* roots, int G, const oaz_pur
         for (int g = 0; g < G; ++g)
             HIP_TRY(hipMemcpyAsync(tree_out + (size_t)g * tree_cap, d_nodes + (size_t)g * cap,
                                    sizeof(oaz_pure_node) * (tree_cap < cap ? tree_cap : cap), hipMemcpyDeviceToHost, sm));
+        HIP_TRY(hipStreamSynchronize(sm));
+    }
+    return 0;
+}
+
+// ---- one search per root, each with its own parameters (bin/mcts_parameter_check.rs's sweep in one launch per ply) --
+namespace {
+size_t each_root_capacity(const oaz_pure_mcts_root& r) {  // oaz_pure_mcts_tree_capacity of (max_playouts, min_node_visits)
+    if (r.max_playouts < 0 || r.min_node_visits < 0) return 0;
+    oaz_pure_mcts_config c{};
+    c.max_playouts = r.max_playouts;
+    c.min_node_visits = r.min_node_visits;
+    return oaz_pure_mcts_tree_capacity(&c);
+}
+}  // namespace
+
+extern "C" size_t oaz_pure_mcts_each_capacity(const oaz_pure_mcts_root* par, int G, size_t* offsets) {
+    size_t total = 0;
+    for (int g = 0; par && g < G; ++g) {
+        if (offsets) offsets[g] = total;
+        total += each_root_capacity(par[g]);
+    }
+    if (offsets && par && G >= 0) offsets[G] = total;
+    return total;
+}
+
+extern "C" int oaz_pure_mcts_search_each(const oaz_state* roots, const oaz_pure_mcts_root* par, int G,
+                                         const oaz_pure_mcts_each_config* cfg, oaz_move* out_move, float* out_value,
+                                         int32_t* out_playouts, oaz_pure_mcts_stats* stats, oaz_pure_node* tree_out,
+                                         const size_t* tree_offsets) {
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "the packed trees' offsets are 64-bit on both sides");
+    if (G < 0 || (G > 0 && (!roots || !par || !out_move || !out_value)) || !cfg)
+        return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: null argument");
+    if (tree_out && !tree_offsets) return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: tree_out without tree_offsets");
+    if (cfg->rollout_cap < 0) return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: negative rollout_cap");
+    if (cfg->search_time_ns < 0) return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: negative search_time_ns");
+    int max_playouts = 0;
+    for (int g = 0; g < G; ++g) {
+        if (par[g].max_playouts < 0 || par[g].min_node_visits < 0)
+            return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d: negative max_playouts / min_node_visits", g);
+        if (par[g].stream >> 32)
+            return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d: stream %llu is not below 2^32", g,
+                               (unsigned long long)par[g].stream);
+        if ((roots[g].to_move & ~1) || (roots[g].cards[0] | roots[g].cards[1] | roots[g].cards[2] | roots[g].cards[3] |
+                                        roots[g].cards[4]) > 15)
+            return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d is not a valid state", g);
+        if (each_root_capacity(par[g]) > 0xFFFFFFF0u)
+            return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d: tree capacity too large", g);
+        if (tree_out && tree_offsets[g + 1] < tree_offsets[g])
+            return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d: tree_offsets decrease", g);
+        if (par[g].max_playouts > max_playouts) max_playouts = par[g].max_playouts;
+    }
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (G == 0) return 0;
+    if (int rc = oaz_check_device("pure_mcts_each", cfg->device)) return rc;
+    if (cfg->device >= kPureMaxDevices)
+        return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: device %d unsupported", cfg->device);
+    std::vector<uint64_t> off((size_t)G + 1);
+    const size_t total = oaz_pure_mcts_each_capacity(par, G, reinterpret_cast<size_t*>(off.data()));
+    std::vector<float> ln((size_t)max_playouts + 2);  // sized by the call's largest search
+    for (size_t n = 0; n < ln.size(); ++n) ln[n] = logf((float)n);
+    pm::EachParams p{cfg->rollout_cap, cfg->search_time_ns > 0 ? 1 : 0, cfg->seed, 0};
+    if (p.clock_on) {  // the budget in ticks of the device's constant-rate clock (as oaz_config.search_time_ns)
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, cfg->device) != hipSuccess || khz <= 0)
+            return oaz_set_err(OAZ_ERR_HIP, "pure_mcts_each: search_time: the device reports no wall clock rate");
+        const double ticks = (double)cfg->search_time_ns * (double)khz * 1e-6;
+        p.ticks = ticks < 9e18 ? (uint64_t)ticks : (uint64_t)9e18;
+    }
+    // the workspace (the device's kept buffer, shared with oaz_pure_mcts_search): roots, parameters, tree offsets,
+    // ln table, values, moves, playouts, statistics, and the trees packed by `off`
+    oaz_state* d_roots = nullptr;
+    oaz_pure_mcts_root* d_par = nullptr;
+    uint64_t *d_off = nullptr, *d_st = nullptr;
+    float *d_ln = nullptr, *d_val = nullptr;
+    oaz_move* d_mv = nullptr;
+    int32_t* d_po = nullptr;
+    oaz_pure_node* d_nodes = nullptr;
+    auto carve = [&](Carver c) {
+        d_roots = c.take<oaz_state>(G);
+        d_par = c.take<oaz_pure_mcts_root>(G);
+        d_off = c.take<uint64_t>((size_t)G + 1);
+        d_ln = c.take<float>(ln.size());
+        d_val = c.take<float>(G);
+        d_mv = c.take<oaz_move>(G);
+        d_po = c.take<int32_t>(G);
+        d_st = c.take<uint64_t>((size_t)8 * G);
+        d_nodes = c.take<oaz_pure_node>(total);
+        return c.off;
+    };
+    const size_t ws_bytes = carve(Carver{nullptr});
+    OAZ_ON_DEVICE(cfg->device);
+    std::vector<uint64_t> st((size_t)G * 8);
+    std::vector<int32_t> po((size_t)G);
+    WorkspaceLease ws;  // (declared before the stream: waited for before the workspace goes back, as above)
+    Stream sm;
+    if (int rc = sm.create()) return rc;
+    if (int rc = ws.acquire(cfg->device, ws_bytes)) return rc;
+    carve(Carver{ws.p});
+    HIP_TRY(hipMemcpyAsync(d_roots, roots, sizeof(oaz_state) * G, hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_par, par, sizeof(oaz_pure_mcts_root) * G, hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_off, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(d_ln, ln.data(), sizeof(float) * ln.size(), hipMemcpyHostToDevice, sm));
+    hipLaunchKernelGGL(pm::k_pure_mcts_each, dim3((G + 63) / 64), dim3(64), 0, sm, d_roots, d_par, d_off, G, p, d_ln,
+                       d_nodes, d_mv, d_val, d_po, d_st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(sm));
+    HIP_TRY(hipMemcpyAsync(out_move, d_mv, sizeof(oaz_move) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(out_value, d_val, sizeof(float) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(po.data(), d_po, sizeof(int32_t) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(st.data(), d_st, sizeof(uint64_t) * st.size(), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipStreamSynchronize(sm));
+    if (out_playouts) memcpy(out_playouts, po.data(), sizeof(int32_t) * G);
+    if (stats)
+        for (int g = 0; g < G; ++g) {
+            stats->playouts += st[g * 8 + 0];
+            stats->expansions += st[g * 8 + 1];
+            stats->rollout_plies += st[g * 8 + 2];
+            stats->rollout_passes += st[g * 8 + 3];
+            stats->rollouts_capped += st[g * 8 + 4];
+            if (st[g * 8 + 5] > stats->max_nodes) stats->max_nodes = st[g * 8 + 5];
+            stats->tree_full += st[g * 8 + 6];
+        }
+    if (tree_out) {
+        // root g's nodes go to tree_out + tree_offsets[g], as many as its slice there holds; with the offsets of
+        // oaz_pure_mcts_each_capacity that is the packed device array as it stands
+        bool same = true;
+        for (int g = 0; g <= G && same; ++g) same = tree_offsets[g] == off[g];
+        if (same) {
+            HIP_TRY(hipMemcpyAsync(tree_out, d_nodes, sizeof(oaz_pure_node) * total, hipMemcpyDeviceToHost, sm));
+        } else {
+            for (int g = 0; g < G; ++g) {
+                const size_t have = off[g + 1] - off[g], room = tree_offsets[g + 1] - tree_offsets[g];
+                HIP_TRY(hipMemcpyAsync(tree_out + tree_offsets[g], d_nodes + off[g],
+                                       sizeof(oaz_pure_node) * (room < have ? room : have), hipMemcpyDeviceToHost, sm));
+            }
+        }
         HIP_TRY(hipStreamSynchronize(sm));
     }
     return 0;

@@ -15,9 +15,10 @@ from .selfplay import SelfPlayData, TrainConfig, self_play
 from .evaluator import (AlphaZeroAgent, EloRating, Evaluator, EvaluatorConfig, FightStatistics, PitStatistics,
                         RandomAgent, fight)
 from .arena import NativeRandomAgent, native_fight
-from .pure_mcts import Mcts, pure_mcts_search
+from .pure_mcts import Mcts, pure_mcts_search, pure_mcts_search_each
 from .alpha_beta import AlphaBeta, alpha_beta_generate_move, alpha_beta_search
 from .tournament import Tournament
+from .parameter_check import ParameterCheck
 from .trainer import Trainer, train_epochs
 from .train_loop import LoopConfig, Stats, train
 
@@ -28,5 +29,5 @@ __all__ = [
     "SelfPlayData", "TrainConfig", "self_play", "AlphaZeroAgent", "EloRating", "Evaluator", "EvaluatorConfig",
     "FightStatistics", "PitStatistics", "RandomAgent", "fight", "Mcts", "pure_mcts_search", "Trainer", "train_epochs",
     "LoopConfig", "Stats", "train", "AlphaBeta", "alpha_beta_search", "NativeRandomAgent", "native_fight",
-    "alpha_beta_generate_move", "Tournament",
+    "alpha_beta_generate_move", "Tournament", "pure_mcts_search_each", "ParameterCheck",
 ]

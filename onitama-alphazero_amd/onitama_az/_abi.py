@@ -174,6 +174,16 @@ class oaz_pure_mcts_stats(C.Structure):
                                           "rollouts_capped", "max_nodes", "tree_full")]
 
 
+class oaz_pure_mcts_root(C.Structure):  # 24 bytes
+    _fields_ = [("max_playouts", C.c_int32), ("min_node_visits", C.c_int32), ("exploration_c", C.c_float),
+                ("reserved", C.c_uint32), ("stream", C.c_uint64)]
+
+
+class oaz_pure_mcts_each_config(C.Structure):  # 32 bytes
+    _fields_ = [("seed", C.c_uint64), ("search_time_ns", C.c_int64), ("rollout_cap", C.c_int32),
+                ("device", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class oaz_alphabeta_config(C.Structure):
     _fields_ = [("max_depth", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32 * 2)]
 
@@ -285,6 +295,9 @@ SAMPLE_DTYPE = np.dtype([("state", STATE_DTYPE), ("pi", "<f4", 50), ("z", "<f4")
 PURE_NODE_DTYPE = np.dtype([("visits", "<u4"), ("reward", "<f4"), ("winrate", "<f4"), ("first", "<u4"),
                             ("parent", "<u4"), ("mv", "<u2"), ("nch", "u1"), ("flags", "u1")])
 assert PURE_NODE_DTYPE.itemsize == 24
+PURE_ROOT_DTYPE = np.dtype([("max_playouts", "<i4"), ("min_node_visits", "<i4"), ("exploration_c", "<f4"),
+                            ("reserved", "<u4"), ("stream", "<u8")])
+assert PURE_ROOT_DTYPE.itemsize == C.sizeof(oaz_pure_mcts_root) == 24 and C.sizeof(oaz_pure_mcts_each_config) == 32
 assert STATE_DTYPE.itemsize == 24 and NODE_DTYPE.itemsize == 32 and SAMPLE_DTYPE.itemsize == 228
 
 # C prototypes: name -> (restype, argtypes)
@@ -351,6 +364,9 @@ _PROTOS = {
     "oaz_pure_mcts_search": (C.c_int, [_VOIDP, C.c_int, _P(oaz_pure_mcts_config), _VOIDP, _VOIDP,
                                        _P(oaz_pure_mcts_stats), _VOIDP, C.c_size_t]),
     "oaz_pure_mcts_release_workspace": (C.c_int, [C.c_int]),
+    "oaz_pure_mcts_each_capacity": (C.c_size_t, [_VOIDP, C.c_int, _VOIDP]),
+    "oaz_pure_mcts_search_each": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _P(oaz_pure_mcts_each_config), _VOIDP, _VOIDP,
+                                            _VOIDP, _P(oaz_pure_mcts_stats), _VOIDP, _VOIDP]),
     "oaz_alphabeta_config_default": (None, [_P(oaz_alphabeta_config)]),
     "oaz_alphabeta_evaluate": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _VOIDP]),
     "oaz_alphabeta_search": (C.c_int, [_VOIDP, C.c_int, _P(oaz_alphabeta_config), _VOIDP, _VOIDP,
