@@ -128,7 +128,9 @@ typedef struct oaz_node {
     uint16_t mv;     /* packed move: from | to<<5 | slot<<10 | piece<<12 */
     uint8_t nch;     /* number of children */
     uint8_t flags;   /* bit0 expanded, bit1 terminal */
-    uint32_t pad;
+    uint32_t pad;    /* 0. With tree reuse the re-rooting kernel uses this word as its scratch while it runs and
+                      * leaves 0 again in every node; only a tree dumped after that kernel was cut short (a
+                      * failed launch, a reset device) can show other values here */
 } oaz_node; /* 32 bytes */
 
 /* Self-play training sample (SelfPlayData, train.rs:27-33): encoded compactly; the 21x5x5
@@ -184,7 +186,14 @@ typedef struct oaz_config {
                                 launch, a workgroup per game doing all its simulations (the Agent API's
                                 one-position latency path); 1 = always the per-simulation-step launches.
                                 Trees, pi and samples are identical either way */
-    int32_t reserved;
+    int32_t reuse_visits;    /* tree reuse (DESIGN.md "Tree reuse"): 0 = off (default): a fresh tree per search
+                                and per self-play ply, the memory and behaviour of an engine without the
+                                feature. R > 0 (R >= sims): a tree's capacity in root visits; trees hold
+                                1 + R * OAZ_MAX_MOVES nodes (device memory for trees grows by R / sims). A
+                                self-play ply, and oaz_search_advance, then keep the played move's subtree for
+                                the next search when the moved-to child is expanded, not terminal-flagged, the
+                                move does not win, and the child's visits + the creation `sims` <= R; the next
+                                search adds `sims` playouts to the kept ones */
 } oaz_config;
 
 typedef struct oaz_search_stats {
@@ -359,6 +368,42 @@ int oaz_search(oaz_engine* eng, const oaz_state* roots, int G, oaz_move* out_mov
 /* Tree of `game` left by the last oaz_search, or of slot `game` by the last self-play ply (the tree that
  * ply's move and pi came from): nodes [0, *n_nodes) in reference arena order. */
 int oaz_tree_dump(oaz_engine* eng, int game, oaz_node* out, int cap, int* n_nodes);
+
+/* ---- tree reuse (oaz_config.reuse_visits > 0; DESIGN.md "Tree reuse") -------------------------
+ * The subtree of a root child c, taken out of a search tree with its node order kept, equals node for node
+ * the tree of a fresh search from c's position with N_c playouts (HASH evaluator, no root noise), so a
+ * search resumed on it for `sims` more playouts equals a fresh search of N_c + sims playouts. */
+typedef struct oaz_reuse_stats {
+    uint64_t trees_kept;   /* searches (self-play plies of playing slots, advanced games) that began on a kept subtree */
+    uint64_t trees_fresh;  /* ... and on a fresh tree (game starts, passes, the keep rule said no) */
+    uint64_t visits_kept;  /* sum of the kept children's N: playouts those searches did not have to redo */
+    uint64_t nodes_kept;   /* sum of the kept subtrees' node counts */
+} oaz_reuse_stats;
+/* Re-roots the first G trees of the last oaz_search / oaz_search_resume at moves[g] and steps the engine's
+ * resident root positions by them (the side to move flips). Where the keep rule holds (oaz_config.reuse_visits)
+ * the moved-to child's subtree becomes the tree and kept[g] (optional, [G]) is that child's N; otherwise the
+ * game gets a fresh tree and kept[g] = 0. A pass (from = to = 25, slot = one of the mover's cards, which goes
+ * round with the neutral card) is accepted only at a root without a child and leaves a fresh tree.
+ * OAZ_ERR_STATE: reuse_visits == 0, the last search covered fewer than G games, or self-play or an arena fight
+ * on this engine ran in between.
+ * OAZ_ERR_ARG: a move that is neither a child of its root nor an accepted pass; the moves are validated by a
+ * kernel that changes nothing, so on this error no tree and no root has changed for any game. */
+int oaz_search_advance(oaz_engine* eng, const oaz_move* moves, int G, int32_t* kept);
+/* oaz_search on the engine's resident roots (the positions oaz_search_advance stepped to; out_roots,
+ * optional [G], receives them) without the tree reset: cfg.sims more playouts per game on the trees as
+ * they are, by the per-simulation-step kernels. Outputs as oaz_search's. OAZ_ERR_STATE: reuse_visits == 0,
+ * no search of at least G games came before, or the trees cannot hold sims more playouts (a second resume
+ * without an advance in between, past reuse_visits root visits). */
+int oaz_search_resume(oaz_engine* eng, int G, oaz_move* out_move, float* out_pi, float* out_root_value,
+                      oaz_search_stats* stats, oaz_state* out_roots);
+/* The counters since creation or the last oaz_selfplay_reset (all 0 with reuse_visits == 0). */
+int oaz_reuse_stats_get(oaz_engine* eng, oaz_reuse_stats* out);
+/* The re-rooting the device does, restated on the host (host only; the compaction is stated once, in
+ * csrc/oaz_tree_rebase.h, for both): in[0, n) is a tree as oaz_tree_dump gives it, child the index among the
+ * root's children (0 .. nch - 1) of a visited child; out[0, *n_out) becomes that child's subtree in the same
+ * node order, `first` indices remapped, the new root with P = 1 and mv = 0. OAZ_ERR_ARG for a child the root
+ * does not have or one with N == 0, OAZ_ERR_CAPACITY when the subtree exceeds cap; nothing is written then. */
+int oaz_tree_rebase_host(const oaz_node* in, int n, int child, oaz_node* out, int cap, int* n_out);
 
 /* ---- self-play (continuous batching over cfg.games slots, device resident) ------ */
 int oaz_selfplay_reset(oaz_engine* eng);                 /* deal a fresh game in every slot */

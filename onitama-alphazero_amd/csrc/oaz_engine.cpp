@@ -28,7 +28,9 @@
 
 using namespace oaz;
 
-static_assert(offsetof(oaz_config, search_time_ns) == 104 && sizeof(oaz_config) == 120, "oaz_config layout (ABI 4)");
+static_assert(offsetof(oaz_config, search_time_ns) == 104 && offsetof(oaz_config, reuse_visits) == 116 &&
+                  sizeof(oaz_config) == 120,
+              "oaz_config layout (ABI 4; reuse_visits took the reserved word)");
 
 // ---- errors ---------------------------------------------------------------------------------
 static thread_local std::string g_err;
@@ -325,6 +327,14 @@ struct oaz_engine {
     DevBuf<unsigned long long> out_count;
     DevBuf<uint32_t> fin;      // SlotView::fin / fin_pos (records of the games that ended in a ply)
     DevBuf<uint64_t> fin_pos;
+    // tree reuse (cfg.reuse_visits > 0; nothing is allocated without it): oaz_search_advance's per-game scratch
+    // (the caller's moves, the validation codes, the kept visits) and the oaz_reuse_stats counters
+    DevBuf<oaz_move> adv_moves;
+    DevBuf<int32_t> adv_codes, adv_kept;
+    DevBuf<uint64_t> reuse_cnt;
+    uint32_t searched = 0;        // games whose trees are the last oaz_search / oaz_search_resume's (0: self-play ran since)
+    int64_t tree_visits = 0;      // the most root visits any of those trees can hold by now
+    bool ply_trees = false;       // the trees are the previous self-play ply's (cleared by oaz_selfplay_reset and any search)
     unsigned long long out_read = 0;  // samples already handed out
     bool selfplay_ready = false;
     uint64_t quota = 0;
@@ -490,6 +500,12 @@ static int timed(oaz_engine* e, LaunchKind kind, uint32_t samples, F&& launch, h
 }
 
 // The argument checks of oaz_create.
+// Root visits a tree is sized for: the playouts of one search, or with tree reuse its capacity R >= sims.
+static uint32_t tree_visits_cap(const oaz_config* cfg) {
+    return (uint32_t)(cfg->reuse_visits > 0 ? cfg->reuse_visits : cfg->sims);
+}
+constexpr int32_t kMaxReuseVisits = 1 << 20;  // 1 + R * OAZ_MAX_MOVES nodes fit 32-bit node indices with room
+
 static int create_check(const oaz_config* cfg, int device) {
     if (!cfg) return oaz_set_err(OAZ_ERR_ARG, "create: null config");
     if (cfg->channels != 64 || cfg->in_planes != 21)
@@ -498,10 +514,16 @@ static int create_check(const oaz_config* cfg, int device) {
         cfg->max_plies < 0 || cfg->max_plies > 100000 || cfg->compact < 0 || cfg->compact > 2 || cfg->search_time_ns < 0 ||
         cfg->step_kernels < 0 || cfg->step_kernels > 1 || cfg->world < 0 || cfg->rank < 0 ||
         cfg->rank >= (cfg->world > 0 ? cfg->world : 1) ||
-        (uint64_t)cfg->games * ((uint64_t)cfg->sims + 1) >= (1ull << 32) ||  // 32-bit path offsets (k_select_seg)
+        cfg->reuse_visits < 0 || cfg->reuse_visits > kMaxReuseVisits ||
+        (uint64_t)cfg->games * ((uint64_t)tree_visits_cap(cfg) + 1) >= (1ull << 32) ||  // 32-bit path offsets (k_select_seg)
         (uint64_t)cfg->games * kNoiseStride * sizeof(noise_t) >= (1ull << 31) ||  // 32-bit noise offsets (root_noise_pairs)
         (cfg->parts != 0 && cfg->parts != 1 && cfg->parts != 2 && cfg->parts != 4))
         return oaz_set_err(OAZ_ERR_ARG, "create: config out of range");
+    if (cfg->reuse_visits > 0 && cfg->reuse_visits < cfg->sims)
+        return oaz_set_err(OAZ_ERR_ARG, "create: reuse_visits=%d < sims=%d (a tree must hold one search)", cfg->reuse_visits,
+                           cfg->sims);
+    if (cfg->reuse_visits > 0 && !launch_selfplay_rebase)
+        return oaz_set_err(OAZ_ERR_ARG, "create: reuse_visits > 0 in a build without the tree reuse kernels");
     if (cfg->precision != OAZ_FP32 && cfg->precision != OAZ_BF16 && cfg->precision != OAZ_FP32_SPLIT &&
         cfg->precision != OAZ_FP32_SPLIT16)
         return oaz_set_err(OAZ_ERR_ARG, "create: precision must be OAZ_FP32, OAZ_BF16, OAZ_FP32_SPLIT or OAZ_FP32_SPLIT16");
@@ -528,7 +550,7 @@ static int engine_init(oaz_engine* e) {
     e->noise_chunk = noise_chunk_for(e);
     if (e->nodes.alloc(G * e->cap) || e->n_nodes.alloc(G) || e->path.alloc(G * e->pathcap) || e->depth.alloc(G) ||
         e->leaf.alloc(G) || e->leaf_state.alloc(G) || e->stats.alloc(G * GS_COUNT) || e->stats_sum.alloc(GS_COUNT) ||
-        e->sqrt_tab.alloc((size_t)cfg->sims + 2) || e->policy.alloc(G * 50) || e->value.alloc(G) || e->need.alloc(G) ||
+        e->sqrt_tab.alloc((size_t)tree_visits_cap(cfg) + 2) || e->policy.alloc(G * 50) || e->value.alloc(G) || e->need.alloc(G) ||
         e->slot.alloc(G) || e->cstate.alloc(G + 16) || e->bcnt.alloc((size_t)buckets_of((uint32_t)G) + kMaxParts) ||
         e->weights.alloc(nn_device_floats(cfg->blocks, cfg->precision)) || e->s_roots.alloc(G) || e->s_move.alloc(G) ||
         e->s_pi.alloc(G * 50) || e->s_rootv.alloc(G) || e->s_rootp.alloc(G * 50) || e->s_ply.alloc(G) ||
@@ -537,8 +559,11 @@ static int engine_init(oaz_engine* e) {
         e->deadline.alloc(1) || e->sims_run.alloc(G) || e->fin.alloc(G) || e->fin_pos.alloc(G) ||
         (cfg->train_noise && e->noise.alloc(2 * (size_t)e->noise_chunk * G * kNoiseStride)))
         return OAZ_ERR_HIP;  // (alloc's HIP_TRY recorded the call and the HIP error)
+    if (cfg->reuse_visits > 0 &&
+        (e->adv_moves.alloc(G) || e->adv_codes.alloc(G) || e->adv_kept.alloc(G) || e->reuse_cnt.alloc(4)))
+        return OAZ_ERR_HIP;
     // sqrt((double)n) from the host libm (IEEE correctly rounded), so device PUCT = oracle PUCT
-    std::vector<double> tab((size_t)cfg->sims + 2);
+    std::vector<double> tab((size_t)tree_visits_cap(cfg) + 2);
     for (size_t i = 0; i < tab.size(); ++i) tab[i] = sqrt((double)i);
     // on the engine's own stream, waited for: its streams do not synchronise with the null stream, a null-stream
     // hipMemset returns before it ran and a pageable hipMemcpy before its DMA landed, so the first kernels could
@@ -552,6 +577,7 @@ static int engine_init(oaz_engine* e) {
     HIP_TRY(hipMemsetAsync(e->need, 0, G, s0));
     HIP_TRY(hipMemsetAsync(e->slot, 0, G * sizeof(uint32_t), s0));
     HIP_TRY(hipMemsetAsync(e->cstate, 0, (G + 16) * sizeof(oaz_state), s0));
+    if (e->reuse_cnt) HIP_TRY(hipMemsetAsync(e->reuse_cnt, 0, 4 * sizeof(uint64_t), s0));
     HIP_TRY(hipStreamSynchronize(s0));
     if (cfg->evaluator == OAZ_EVAL_NN) {  // random-init weights until oaz_load_weights
         std::vector<float> w(oaz_weight_count(cfg->blocks, 64, 21));
@@ -568,8 +594,8 @@ extern "C" oaz_engine* oaz_create(const oaz_config* cfg, int device) {
     e->device = device;
     e->G = (uint32_t)cfg->games;
     e->sims_cap = cfg->sims;
-    e->cap = 1u + (uint32_t)cfg->sims * OAZ_MAX_MOVES;  // each playout expands <= 1 node of <= 40 children
-    e->pathcap = (uint32_t)cfg->sims + 1;               // depth grows by <= 1 per playout
+    e->cap = 1u + tree_visits_cap(cfg) * OAZ_MAX_MOVES;  // each playout expands <= 1 node of <= 40 children
+    e->pathcap = tree_visits_cap(cfg) + 1;               // depth grows by <= 1 per playout
     e->hcap = (uint32_t)cfg->max_plies + 2;             // train.rs:74-79 cut after max_plies+2 plies
     e->out_cap = cfg->sample_capacity > 0 ? (uint32_t)cfg->sample_capacity : e->G * 64u;
     if (engine_init(e)) {  // the one failure exit: the partly built engine goes, the error text stays
@@ -773,10 +799,10 @@ static bool compact_leaves(const oaz_engine* e, uint32_t G) {
 //          between steps;
 //   GRP    k_search_grp: 16 games per workgroup, up to one round of workgroups, one launch per root-noise
 //          chunk (any G below a qualifying engine's qualifies as well);
-//   STEPS  the per-simulation-step launches.
+//   STEPS  the per-simulation-step launches; always so for a search that goes on with kept trees (tree reuse).
 enum SearchPath { PATH_LAT, PATH_GRP, PATH_STEPS };
-static SearchPath search_path(const oaz_engine* e, uint32_t G, bool noise) {
-    const bool one_launch = e->cfg.step_kernels == 0 && !compact_leaves(e, G) &&
+static SearchPath search_path(const oaz_engine* e, uint32_t G, bool noise, bool kept_trees = false) {
+    const bool one_launch = !kept_trees && e->cfg.step_kernels == 0 && !compact_leaves(e, G) &&
                             (e->cfg.evaluator == OAZ_EVAL_HASH || e->cfg.precision == OAZ_FP32_SPLIT16) &&
                             tree_seg_kernels();
     if (!one_launch) return PATH_STEPS;
@@ -791,7 +817,8 @@ static SearchPath search_path(const oaz_engine* e, uint32_t G, bool noise) {
 // noise overlaps the network and the first select waits for only 16 simulations' draws. Ring: 2 x chunk x
 // G x 80 floats (<= 1.3 GB at 4 096 games).
 static uint32_t noise_chunk_for(const oaz_engine* e) {
-    if (search_path(e, e->G, true) != PATH_GRP) return kNoiseChunk;
+    // (an engine with tree reuse goes on with kept trees, which run the per-step launches at every size)
+    if (search_path(e, e->G, true, e->cfg.reuse_visits > 0) != PATH_GRP) return kNoiseChunk;
     return std::max(kNoiseChunk, std::min((uint32_t)e->sims_cap, 512u));
 }
 
@@ -1063,9 +1090,9 @@ static int run_chunks(oaz_engine* e, const Search& S, bool grp) {
 // joined into the engine stream anyway (all of them, whatever the number of parts was: the drivers' early
 // returns skip the join), so oaz_sync and buffer reuse after an error wait for them.
 static int run_sims(oaz_engine* e, const TreeView& t, const oaz_state* roots, const uint8_t* active,
-                    const uint64_t* gids, const uint32_t* plies) {
+                    const uint64_t* gids, const uint32_t* plies, bool kept_trees = false) {
     const bool budget = e->cfg.search_time_ns > 0, noise = e->cfg.train_noise && e->noise;
-    const SearchPath path = search_path(e, t.G, noise);
+    const SearchPath path = search_path(e, t.G, noise, kept_trees);
     const NNView w = nn_view(e, nullptr);
     Search S{t, roots, active, gids, plies, search_params(e), (uint32_t)e->cfg.sims, noise,
              e->cfg.evaluator == OAZ_EVAL_HASH ? nullptr : &w, budget ? e->deadline.get() : nullptr,
@@ -1110,7 +1137,12 @@ static void fill_search_stats(const uint64_t* s, oaz_search_stats* o) {
 // to s_roots first, or with roots == null the G positions already in s_roots are searched (the arena's
 // device-resident fight, oaz_arena.hip). The moves are left in s_move and pi in s_pi. Without a search_time
 // budget nothing here waits for the device.
-static int search_core(oaz_engine* e, const oaz_state* roots, int G) {
+// keep_trees (oaz_search_resume): no tree reset; the playouts go on with the first G trees as they are. Any
+// search ends what tree reuse may go on from (`searched` = 0); oaz_search and oaz_search_resume, the two searches
+// oaz_search_advance follows, set it again (searched_trees), the arena's resident search does not.
+static int search_core(oaz_engine* e, const oaz_state* roots, int G, bool keep_trees = false) {
+    e->ply_trees = false;
+    e->searched = 0;
     if (int rc = begin_budget(e)) return rc;
     const TreeView t = tree_view(e, (uint32_t)G);
     if (roots) HIP_TRY(hipMemcpyAsync(e->s_roots, roots, (size_t)G * sizeof(oaz_state), hipMemcpyHostToDevice, e->stream));
@@ -1118,8 +1150,8 @@ static int search_core(oaz_engine* e, const oaz_state* roots, int G) {
     // every root's "ply" (the root-noise key) is the number of this engine's earlier searches
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)e->s_ply.get(), (int)e->search_calls, (size_t)G, e->stream));
     e->search_calls++;
-    HIP_TRY(launch_tree_reset(t, e->stream));
-    if (int rc = run_sims(e, t, e->s_roots, nullptr, nullptr, e->s_ply)) return rc;
+    if (!keep_trees) HIP_TRY(launch_tree_reset(t, e->stream));
+    if (int rc = run_sims(e, t, e->s_roots, nullptr, nullptr, e->s_ply, keep_trees)) return rc;
     return timed(e, K_FINALIZE, (uint32_t)G,
                  [&] { return launch_search_finalize(t, e->s_roots, e->s_move, e->s_pi, e->stream); });
 }
@@ -1139,18 +1171,18 @@ int oaz_engine_search_resident(oaz_engine* e, int G) {
     return G == 0 ? 0 : search_core(e, nullptr, G);
 }
 
-extern "C" int oaz_search(oaz_engine* e, const oaz_state* roots, int G, oaz_move* out_move, float* out_pi,
-                          float* out_root_value, oaz_search_stats* stats) {
-    if (!e || !roots || G < 0) return oaz_set_err(OAZ_ERR_ARG, "search: bad arguments");
-    if ((uint32_t)G > e->G) return oaz_set_err(OAZ_ERR_CAPACITY, "search: G=%d > games=%u", G, e->G);
-    if (G == 0) return 0;
-    for (int i = 0; i < G; ++i)
-        if (roots[i].to_move > 1) return oaz_set_err(OAZ_ERR_ARG, "search: root %d has to_move=%d", i, roots[i].to_move);
-    OAZ_ON_DEVICE(e->device);
-    if (int rc = search_core(e, roots, G)) {
-        (void)hipStreamSynchronize(e->stream);  // the roots upload reads the caller's buffer
-        return rc;
-    }
+// After search_core in oaz_search / oaz_search_resume: the first G trees are what oaz_search_advance may re-root,
+// and hold at most `visits` root visits.
+static void searched_trees(oaz_engine* e, int G, int64_t visits) {
+    e->searched = (uint32_t)G;
+    e->tree_visits = visits;
+}
+
+// What oaz_search and oaz_search_resume hand back after search_core: the optional extra root evaluation, the
+// moves, pi and resident roots to the host, then the statistics. Waits for the engine stream.
+static int search_results(oaz_engine* e, int G, oaz_move* out_move, float* out_pi, float* out_root_value,
+                          oaz_search_stats* stats, oaz_state* out_roots) {
+    if (out_roots) HIP_TRY(hipMemcpyAsync(out_roots, e->s_roots, (size_t)G * sizeof(oaz_state), hipMemcpyDeviceToHost, e->stream));
     if (out_root_value) {  // extra root evaluation (alphazero_mcts/mod.rs:137-141)
         if (int rc = evaluate(e, e->s_roots, (uint32_t)G, e->s_rootp, e->s_rootv)) return rc;
         HIP_TRY(hipMemcpyAsync(out_root_value, e->s_rootv, (size_t)G * 4, hipMemcpyDeviceToHost, e->stream));
@@ -1164,6 +1196,53 @@ extern "C" int oaz_search(oaz_engine* e, const oaz_state* roots, int G, oaz_move
         memset(stats, 0, sizeof(*stats));
         fill_search_stats(s, stats);
     }
+    return 0;
+}
+
+extern "C" int oaz_search(oaz_engine* e, const oaz_state* roots, int G, oaz_move* out_move, float* out_pi,
+                          float* out_root_value, oaz_search_stats* stats) {
+    if (!e || !roots || G < 0) return oaz_set_err(OAZ_ERR_ARG, "search: bad arguments");
+    if ((uint32_t)G > e->G) return oaz_set_err(OAZ_ERR_CAPACITY, "search: G=%d > games=%u", G, e->G);
+    if (G == 0) return 0;
+    for (int i = 0; i < G; ++i)
+        if (roots[i].to_move > 1) return oaz_set_err(OAZ_ERR_ARG, "search: root %d has to_move=%d", i, roots[i].to_move);
+    OAZ_ON_DEVICE(e->device);
+    if (int rc = search_core(e, roots, G)) {
+        (void)hipStreamSynchronize(e->stream);  // the roots upload reads the caller's buffer
+        return rc;
+    }
+    searched_trees(e, G, e->cfg.sims);
+    return search_results(e, G, out_move, out_pi, out_root_value, stats, nullptr);
+}
+
+// Tree reuse: oaz_search on the resident roots, going on with the trees as oaz_search_advance left them.
+extern "C" int oaz_search_resume(oaz_engine* e, int G, oaz_move* out_move, float* out_pi, float* out_root_value,
+                                 oaz_search_stats* stats, oaz_state* out_roots) {
+    if (!e || G < 0) return oaz_set_err(OAZ_ERR_ARG, "search_resume: bad arguments");
+    if (e->cfg.reuse_visits <= 0) return oaz_set_err(OAZ_ERR_STATE, "search_resume: the engine was made with reuse_visits = 0");
+    if ((uint32_t)G > e->searched)
+        return oaz_set_err(OAZ_ERR_STATE, "search_resume: G=%d, but the trees of %u games are the last search's", G, e->searched);
+    if (e->tree_visits + e->cfg.sims > e->cfg.reuse_visits)
+        return oaz_set_err(OAZ_ERR_STATE, "search_resume: %lld root visits + %d playouts exceed reuse_visits=%d",
+                           (long long)e->tree_visits, e->cfg.sims, e->cfg.reuse_visits);
+    if (G == 0) return 0;
+    OAZ_ON_DEVICE(e->device);
+    const int64_t visits = e->tree_visits + e->cfg.sims;
+    if (int rc = search_core(e, nullptr, G, true)) return rc;
+    searched_trees(e, G, visits);
+    return search_results(e, G, out_move, out_pi, out_root_value, stats, out_roots);
+}
+
+// Engine internals used by tree reuse (oaz_tree_reuse.hip, declared in oaz_host.h).
+int oaz_engine_reuse_view(oaz_engine* e, oaz_reuse_engine_view* out) {
+    if (!e || !out) return oaz_set_err(OAZ_ERR_ARG, "tree reuse: null engine");
+    *out = {e->device, e->searched, e->cap, e->cfg.reuse_visits, e->sims_cap, e->nodes, e->n_nodes, e->s_roots,
+            e->adv_moves, e->adv_codes, e->adv_kept, e->reuse_cnt, e->stream};
+    return 0;
+}
+int oaz_engine_reuse_advanced(oaz_engine* e, int G, int32_t most) {
+    e->searched = (uint32_t)G;
+    e->tree_visits = most;
     return 0;
 }
 
@@ -1190,6 +1269,9 @@ extern "C" int oaz_selfplay_reset(oaz_engine* e) {
     HIP_TRY(hipMemsetAsync(e->stats, 0, (size_t)e->G * GS_COUNT * sizeof(uint64_t), e->stream));
     HIP_TRY(hipMemsetAsync(e->out_count, 0, sizeof(unsigned long long), e->stream));
     e->out_read = 0;
+    if (e->reuse_cnt) HIP_TRY(hipMemsetAsync(e->reuse_cnt, 0, 4 * sizeof(uint64_t), e->stream));
+    e->ply_trees = false;
+    e->searched = 0;
     HIP_TRY(launch_selfplay_reset(t, slot_view(e), e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->selfplay_ready = true;
@@ -1205,9 +1287,16 @@ extern "C" int oaz_selfplay_step(oaz_engine* e, int moves) {
     const SlotView sv = slot_view(e);
     for (int m = 0; m < moves; ++m) {
         if (int rc = begin_budget(e)) return rc;
-        HIP_TRY(launch_tree_reset(t, e->stream));  // a fresh tree per move (the last ply's stays dumpable)
-        if (int rc = run_sims(e, t, e->root, e->active, e->game_id, e->ply)) return rc;
+        const bool reuse = e->cfg.reuse_visits > 0;
+        e->searched = 0;
+        if (!reuse)
+            HIP_TRY(launch_tree_reset(t, e->stream));  // a fresh tree per move (the last ply's stays dumpable)
+        else  // tree reuse: the played move's subtree where the keep rule holds, a fresh root elsewhere
+            HIP_TRY(launch_selfplay_rebase(t, sv, e->ply_trees, e->sims_cap, e->cfg.reuse_visits, e->reuse_cnt, e->stream));
+        e->ply_trees = false;
+        if (int rc = run_sims(e, t, e->root, e->active, e->game_id, e->ply, reuse)) return rc;
         if (int rc = timed(e, K_FINALIZE, e->G, [&] { return launch_selfplay_move(t, sv, e->stream); })) return rc;
+        e->ply_trees = true;
     }
     return 0;
 }

@@ -1,6 +1,8 @@
 // oaz_gpu.hip — one translation unit for the rules / search kernels (oaz_kernels.hip), the network
-// kernels (oaz_nn.hip) and the one-launch small-batch search (oaz_search_lat.hip), which inlines the
-// device bodies of both (tree walk + network in one workgroup).
+// kernels (oaz_nn.hip), the one-launch small-batch search (oaz_search_lat.hip), which inlines the
+// device bodies of both (tree walk + network in one workgroup), and tree reuse (oaz_tree_reuse.hip), which
+// uses the tree kernels' device helpers.
 #include "oaz_kernels.hip"
 #include "oaz_nn.hip"
 #include "oaz_search_lat.hip"
+#include "oaz_tree_reuse.hip"

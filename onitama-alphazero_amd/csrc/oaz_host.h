@@ -183,6 +183,26 @@ struct oaz_arena_engine_view {
 int oaz_engine_arena_view(oaz_engine* e, oaz_arena_engine_view* out);
 int oaz_engine_search_resident(oaz_engine* e, int G);
 
+// Engine internals used by tree reuse (oaz_tree_reuse.hip: oaz_search_advance, oaz_reuse_stats_get): the trees,
+// the resident roots, per-game scratch (allocated with reuse_visits > 0 only: the caller's moves, the
+// validation codes, the kept visits), the oaz_reuse_stats counters, and `searched` = the games whose trees are
+// the last oaz_search / oaz_search_resume's (0 after self-play). oaz_engine_reuse_advanced records that the
+// first G trees now hold at most `most` root visits.
+struct oaz_reuse_engine_view {
+    int device;
+    uint32_t searched, cap;
+    int32_t reuse_visits, sims_cap;
+    oaz_node* nodes;
+    uint32_t* n_nodes;
+    oaz_state* roots;
+    oaz_move* moves;
+    int32_t *codes, *kept;
+    uint64_t* counters;
+    hipStream_t stream;
+};
+int oaz_engine_reuse_view(oaz_engine* e, oaz_reuse_engine_view* out);
+int oaz_engine_reuse_advanced(oaz_engine* e, int G, int32_t most);
+
 // Engine internals used by the communicator (oaz_comm.cpp).
 int oaz_engine_samples_peek(oaz_engine* e, const oaz_sample** dev, size_t* n, int* device);
 int oaz_engine_samples_consume(oaz_engine* e, size_t n);

@@ -158,5 +158,12 @@ hipError_t launch_selfplay_move(const TreeView& t, const SlotView& s, hipStream_
 hipError_t launch_selfplay_reset(const TreeView& t, const SlotView& s, hipStream_t st);
 hipError_t launch_stats_reduce(const uint64_t* per_game, uint32_t G, uint64_t* out /* GS_COUNT */,
                                hipStream_t st);
+// Tree reuse (oaz_tree_reuse.hip), in place of launch_tree_reset between two self-play plies: a slot that goes on
+// with its game keeps the played move's subtree when the keep rule holds (sims_cap, R = reuse_visits), every
+// other slot gets a fresh root; prev = the trees are the previous ply's. counters: the oaz_reuse_stats fields.
+// A weak declaration: the engine's host code also links without oaz_tree_reuse.hip (a host-only build with
+// stand-in launchers), where an engine with reuse_visits > 0 cannot be made.
+__attribute__((weak)) hipError_t launch_selfplay_rebase(const TreeView& t, const SlotView& s, int prev, int32_t sims_cap,
+                                                        int32_t R, uint64_t* counters, hipStream_t st);
 
 }  // namespace oaz

@@ -22,6 +22,7 @@ FP32, BF16, FP32_SPLIT, FP32_SPLIT16 = 0, 1, 2, 3  # OAZ_FP32 / OAZ_BF16 / OAZ_F
 ERR_ARG = -1
 ERR_RANGE = -7  # OAZ_ERR_RANGE (ABI 1 only; ABI 2 recomputes fp16-range tiles, oaz_nn_fallbacks)
 ERR_CAPACITY = -4
+ERR_STATE = -5
 ERR_COMM = -8
 ABI_VERSION = 5
 MAX_MOVES = 40
@@ -88,7 +89,7 @@ class oaz_config(C.Structure):
         ("parts", C.c_int32),
         ("search_time_ns", C.c_int64),
         ("step_kernels", C.c_int32),
-        ("reserved", C.c_int32),
+        ("reuse_visits", C.c_int32),
     ]
 
 
@@ -103,6 +104,10 @@ class oaz_search_stats(C.Structure):
         ("max_nodes", C.c_uint64),
         ("nn_evals", C.c_uint64),
     ]
+
+
+class oaz_reuse_stats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("trees_kept", "trees_fresh", "visits_kept", "nodes_kept")]
 
 
 class oaz_selfplay_stats(C.Structure):
@@ -280,6 +285,7 @@ assert C.sizeof(oaz_move) == 4
 assert C.sizeof(oaz_node) == 32
 assert C.sizeof(oaz_sample) == 228
 assert C.sizeof(oaz_config) == 120 and oaz_config.search_time_ns.offset == 104
+assert oaz_config.reuse_visits.offset == 116 and C.sizeof(oaz_reuse_stats) == 32
 assert C.sizeof(oaz_arena_agent) == 88 and C.sizeof(oaz_arena_config) == 40 and C.sizeof(oaz_fight_stats) == 96
 assert C.sizeof(oaz_arena_slots_stats) == 40
 
@@ -345,6 +351,10 @@ _PROTOS = {
     "oaz_nn_fallbacks": (C.c_int, [_VOIDP, _P(C.c_uint64)]),
     "oaz_search": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _VOIDP, _VOIDP, _VOIDP, _P(oaz_search_stats)]),
     "oaz_tree_dump": (C.c_int, [_VOIDP, C.c_int, _VOIDP, C.c_int, _P(C.c_int)]),
+    "oaz_search_advance": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _VOIDP]),
+    "oaz_search_resume": (C.c_int, [_VOIDP, C.c_int, _VOIDP, _VOIDP, _VOIDP, _P(oaz_search_stats), _VOIDP]),
+    "oaz_reuse_stats_get": (C.c_int, [_VOIDP, _P(oaz_reuse_stats)]),
+    "oaz_tree_rebase_host": (C.c_int, [_VOIDP, C.c_int, C.c_int, _VOIDP, C.c_int, _P(C.c_int)]),
     "oaz_selfplay_reset": (C.c_int, [_VOIDP]),
     "oaz_selfplay_step": (C.c_int, [_VOIDP, C.c_int]),
     "oaz_selfplay_stats_get": (C.c_int, [_VOIDP, _P(oaz_selfplay_stats)]),

@@ -16,6 +16,7 @@ class SearchResult:
     pi: np.ndarray           # [G, 2, 25] float32
     root_value: Optional[np.ndarray]  # [G] float32 (extra root evaluation)
     stats: _abi.oaz_search_stats
+    roots: Optional[np.ndarray] = None  # [G] STATE_DTYPE: the positions searched (Engine.resume only)
 
 
 class Engine:
@@ -124,6 +125,34 @@ class Engine:
         out = np.zeros(n.value, dtype=_abi.NODE_DTYPE)
         _abi.check(self._lib.oaz_tree_dump(self._h, game, _abi.ptr(out), n.value, C.byref(n)))
         return out
+
+    # -- tree reuse (Engine(reuse_visits=R), R >= sims: a tree's capacity in root visits) --
+    def advance(self, moves: np.ndarray) -> np.ndarray:
+        """Re-roots the trees of the last search / resume at moves[g] and steps the engine's resident roots by
+        them. Returns kept [G] int32: the visits of the kept subtree's root, 0 where the game got a fresh tree
+        (the keep rule, oaz_config.reuse_visits)."""
+        moves = np.ascontiguousarray(moves, dtype=_abi.MOVE_DTYPE)
+        kept = np.zeros(len(moves), dtype=np.int32)
+        _abi.check(self._lib.oaz_search_advance(self._h, _abi.ptr(moves), len(moves), _abi.ptr(kept)))
+        return kept
+
+    def resume(self, G: int, root_value: bool = False) -> SearchResult:
+        """`sims` more playouts on the first G trees as advance() left them, from the resident roots
+        (returned as SearchResult.roots)."""
+        G = int(G)
+        moves = np.zeros(G, dtype=_abi.MOVE_DTYPE)
+        pi = np.zeros((G, 2, 25), dtype=np.float32)
+        rv = np.zeros(G, dtype=np.float32) if root_value else None
+        roots = np.zeros(G, dtype=_abi.STATE_DTYPE)
+        st = _abi.oaz_search_stats()
+        _abi.check(self._lib.oaz_search_resume(self._h, G, _abi.ptr(moves), _abi.ptr(pi),
+                                               _abi.ptr(rv) if rv is not None else None, C.byref(st), _abi.ptr(roots)))
+        return SearchResult(moves, pi, rv, st, roots)
+
+    def reuse_stats(self) -> _abi.oaz_reuse_stats:
+        st = _abi.oaz_reuse_stats()
+        _abi.check(self._lib.oaz_reuse_stats_get(self._h, C.byref(st)))
+        return st
 
     # -- self-play --
     def selfplay_reset(self) -> None:

@@ -52,6 +52,7 @@ class LoopConfig:  # TrainConfig, train.rs:100-154 (defaults of Default::default
     deck: Optional[Deck] = None
     evaluator_config: EvaluatorConfig = field(default_factory=EvaluatorConfig)
     seed: int = 20260101
+    reuse_visits: int = 0  # self-play tree reuse (oaz_config.reuse_visits): 0 = a fresh tree per ply, as the reference
 
 
 @dataclass
@@ -109,7 +110,7 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
             kw = dict(games=max(1, min(per_rank, 65536)), sims=mc.max_playouts, c_puct=mc.exploration_c,
                       train_noise=int(mc.train), blocks=blocks, max_plies=config.max_plies, evaluator=_abi.EVAL_NN,
                       precision=options.precision, seed=config.seed + it, rank=rank, world=world,
-                      sample_capacity=max(1, per_rank) * (config.max_plies + 2))
+                      sample_capacity=max(1, per_rank) * (config.max_plies + 2), reuse_visits=config.reuse_visits)
             if config.deck is not None:
                 kw.update(fixed_deck=1, deck=config.deck.indices())
             with Engine(device=options.device, **kw) as eng:
