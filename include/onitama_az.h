@@ -156,8 +156,15 @@ typedef struct oaz_config {
     int32_t precision;       /* OAZ_FP32, OAZ_BF16, OAZ_FP32_SPLIT or OAZ_FP32_SPLIT16 (default) */
     int32_t fixed_deck;      /* 1: every game uses deck[]; 0: random 5 of 16 per game (deck.rs:139-151) */
     uint8_t deck[5];
-    uint8_t pad0[3];
-    uint64_t seed;           /* counter-based RNG key for deals and Dirichlet noise */
+    uint8_t temperature_plies; /* self-play temperature (DESIGN.md "Self-play temperature"): 0 = off (default, and
+                                what a zeroed pad byte of an older caller means): every ply plays the most
+                                visited move. T > 0: in a game's first T plies (ply < T) the played move is drawn
+                                in proportion to the root children's visits (tau = 1, exact in integers, keyed
+                                by seed, game id and ply: oaz_temperature_pick); later plies play the most
+                                visited move. The recorded pi is the visit distribution either way. Self-play
+                                only: oaz_search, the arena and the Agent API ignore it */
+    uint8_t pad0[2];
+    uint64_t seed;           /* counter-based RNG key for deals, Dirichlet noise and temperature draws */
     int32_t rank;            /* global game id = (k * world + rank) * games + slot */
     int32_t world;
     int32_t sample_capacity; /* max samples buffered on the device (0: auto) */
@@ -277,6 +284,13 @@ void oaz_hash_eval(const oaz_state* s, float policy[50], float* value);
  * of global game `game_id`. Host computation of the exact value the GPU's root-noise kernel stores. */
 double oaz_root_noise(uint64_t seed, uint64_t game_id, uint32_t ply, uint32_t sim, uint32_t draw, double alpha,
                       int nchild);
+/* The self-play temperature rule (oaz_config.temperature_plies), restated on the host; needs no device. The root's
+ * children j = 0 .. K-1 in node order have visits[j], S = their sum (uint32; a tree's fits). With w = word 0 of
+ * Philox(seed; game_id lo, game_id hi, 0x54454D50, ply) and r = (w * S) >> 32, the played child is the first j
+ * whose inclusive prefix sum visits[0] + .. + visits[j] exceeds r. Returns that child; -1 when the rule draws
+ * nothing (K <= 0, null visits or S == 0: the pass or the most visited child is played, as without temperature).
+ * T does not enter: whether ply < T is the caller's question. */
+int oaz_temperature_pick(uint64_t seed, uint64_t game_id, uint32_t ply, const uint32_t* visits, int K);
 
 /* ---- rules on the GPU (bit-exact with the reference) ---------------------------- */
 /* Legal moves of s[i].to_move. masks[i][k][from] = destination mask of own piece on
@@ -404,11 +418,23 @@ int oaz_reuse_stats_get(oaz_engine* eng, oaz_reuse_stats* out);
  * node order, `first` indices remapped, the new root with P = 1 and mv = 0. OAZ_ERR_ARG for a child the root
  * does not have or one with N == 0, OAZ_ERR_CAPACITY when the subtree exceeds cap; nothing is written then. */
 int oaz_tree_rebase_host(const oaz_node* in, int n, int child, oaz_node* out, int cap, int* n_out);
+/* After an oaz_search / oaz_search_resume of at least G games: the move the temperature rule draws from game g's
+ * resident tree for (game_ids[g], plies[g]) under cfg.seed, for a caller that drives its own game loop (the
+ * generate_move_tensor of a sampling agent) and as the direct handle on the device's draw. cfg.temperature_plies
+ * does not enter. out_moves [G] and out_child [G] (either may be null): the drawn child's move and its index among
+ * the root's children; the most visited child (the last maximum) where no child has a visit; the pass move of
+ * oaz_search and child -1 at a root without a child. The trees are not changed.
+ * OAZ_ERR_STATE: the last search covered fewer than G games, or self-play or an arena fight ran in between. */
+int oaz_search_sample_moves(oaz_engine* eng, int G, const uint64_t* game_ids, const uint32_t* plies,
+                            oaz_move* out_moves, int32_t* out_child);
 
 /* ---- self-play (continuous batching over cfg.games slots, device resident) ------ */
 int oaz_selfplay_reset(oaz_engine* eng);                 /* deal a fresh game in every slot */
 int oaz_selfplay_step(oaz_engine* eng, int moves);       /* play `moves` plies in every slot */
 int oaz_selfplay_stats_get(oaz_engine* eng, oaz_selfplay_stats* out);
+/* Self-play temperature, since creation or the last oaz_selfplay_reset: out[0] = plies whose move was drawn from
+ * the visits, out[1] = those whose drawn child is not the most visited one (both 0 with temperature_plies == 0). */
+int oaz_selfplay_temperature_stats(oaz_engine* eng, uint64_t out[2]);
 /* Copy up to cap buffered samples to host memory and drop them from the device buffer. */
 int oaz_samples_fetch(oaz_engine* eng, oaz_sample* out, size_t cap, size_t* n_out);
 /* Device-to-device copy of up to cap_bytes/sizeof(oaz_sample) buffered samples into a

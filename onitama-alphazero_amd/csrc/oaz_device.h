@@ -326,6 +326,35 @@ OAZ_HD uint64_t slot_game_id(uint64_t seq, uint32_t world, uint32_t rank, uint32
     return (seq * (uint64_t)world + (uint64_t)rank) * (uint64_t)G + (uint64_t)g;
 }
 
+// ---- self-play temperature (oaz_config.temperature_plies; DESIGN.md "Self-play temperature") -------------
+// In the first T plies of a self-play game the played move is drawn in proportion to the root children's visits
+// (tau = 1), in integers: with S = the sum of the visits n_0 .. n_{K-1} (uint32) and w = word 0 of
+// Philox(seed; game lo, game hi, 0x54454D50 "TEMP", ply), r = (w * S) >> 32 is uniform on [0, S) and the played
+// child is the first j whose inclusive prefix sum n_0 + .. + n_j exceeds r: child j with probability n_j / S up
+// to 2^-32 S, a child without visits never. The tag is >= 2^24, so no root-noise word (ply << 16 | sim) equals it.
+constexpr uint32_t kTemperatureTag = 0x54454D50u;
+OAZ_HD uint32_t temperature_draw(uint64_t seed, uint64_t game, uint32_t ply, uint32_t S) {
+    const u32x4 w = philox(seed, (uint32_t)game, (uint32_t)(game >> 32), kTemperatureTag, ply);
+    return (uint32_t)(((uint64_t)w.x * (uint64_t)S) >> 32);
+}
+// The child the rule draws at ply `ply` of game `game`, or -1 when it draws nothing (no child, or no visit: the
+// pass or the arg-max of visits is then played as without temperature). One body for the host entry
+// (oaz_temperature_pick); the kernels' wave form (wave_temperature_pick, oaz_kernels.hip) is this with a lane per
+// child.
+OAZ_HD int temperature_draw_child(uint64_t seed, uint64_t game, uint32_t ply, const uint32_t* visits, int K) {
+    if (K <= 0) return -1;
+    uint32_t S = 0;
+    for (int j = 0; j < K; ++j) S += visits[j];
+    if (S == 0) return -1;
+    const uint32_t r = temperature_draw(seed, game, ply, S);
+    uint32_t acc = 0;
+    for (int j = 0; j < K; ++j) {
+        acc += visits[j];
+        if (acc > r) return j;
+    }
+    return -1;  // (never reached: r < S)
+}
+
 OAZ_HD uint64_t splitmix64(uint64_t x) {
     uint64_t z = x + 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

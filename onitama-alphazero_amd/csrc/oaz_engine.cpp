@@ -141,6 +141,11 @@ extern "C" double oaz_root_noise(uint64_t seed, uint64_t game_id, uint32_t ply, 
     return (double)root_noise(seed, game_id, (ply << 16) | (sim & 0xFFFFu), draw, alpha, nchild);
 }
 
+extern "C" int oaz_temperature_pick(uint64_t seed, uint64_t game_id, uint32_t ply, const uint32_t* visits, int K) {
+    if (!visits) return -1;
+    return temperature_draw_child(seed, game_id, ply, visits, K);
+}
+
 extern "C" void oaz_hash_eval(const oaz_state* s, float policy[50], float* value) {
     const uint64_t h = hash_state(*s);
     for (int i = 0; i < 50; ++i) policy[i] = hash_policy(h, i);
@@ -332,6 +337,7 @@ struct oaz_engine {
     DevBuf<oaz_move> adv_moves;
     DevBuf<int32_t> adv_codes, adv_kept;
     DevBuf<uint64_t> reuse_cnt;
+    DevBuf<uint64_t> temp_cnt;    // self-play temperature (cfg.temperature_plies > 0 only): oaz_selfplay_temperature_stats
     uint32_t searched = 0;        // games whose trees are the last oaz_search / oaz_search_resume's (0: self-play ran since)
     int64_t tree_visits = 0;      // the most root visits any of those trees can hold by now
     bool ply_trees = false;       // the trees are the previous self-play ply's (cleared by oaz_selfplay_reset and any search)
@@ -524,6 +530,8 @@ static int create_check(const oaz_config* cfg, int device) {
                            cfg->sims);
     if (cfg->reuse_visits > 0 && !launch_selfplay_rebase)
         return oaz_set_err(OAZ_ERR_ARG, "create: reuse_visits > 0 in a build without the tree reuse kernels");
+    if (cfg->temperature_plies > 0 && !launch_selfplay_move_temp)
+        return oaz_set_err(OAZ_ERR_ARG, "create: temperature_plies > 0 in a build without the temperature kernel");
     if (cfg->precision != OAZ_FP32 && cfg->precision != OAZ_BF16 && cfg->precision != OAZ_FP32_SPLIT &&
         cfg->precision != OAZ_FP32_SPLIT16)
         return oaz_set_err(OAZ_ERR_ARG, "create: precision must be OAZ_FP32, OAZ_BF16, OAZ_FP32_SPLIT or OAZ_FP32_SPLIT16");
@@ -562,6 +570,7 @@ static int engine_init(oaz_engine* e) {
     if (cfg->reuse_visits > 0 &&
         (e->adv_moves.alloc(G) || e->adv_codes.alloc(G) || e->adv_kept.alloc(G) || e->reuse_cnt.alloc(4)))
         return OAZ_ERR_HIP;
+    if (cfg->temperature_plies > 0 && e->temp_cnt.alloc(2)) return OAZ_ERR_HIP;
     // sqrt((double)n) from the host libm (IEEE correctly rounded), so device PUCT = oracle PUCT
     std::vector<double> tab((size_t)tree_visits_cap(cfg) + 2);
     for (size_t i = 0; i < tab.size(); ++i) tab[i] = sqrt((double)i);
@@ -578,6 +587,7 @@ static int engine_init(oaz_engine* e) {
     HIP_TRY(hipMemsetAsync(e->slot, 0, G * sizeof(uint32_t), s0));
     HIP_TRY(hipMemsetAsync(e->cstate, 0, (G + 16) * sizeof(oaz_state), s0));
     if (e->reuse_cnt) HIP_TRY(hipMemsetAsync(e->reuse_cnt, 0, 4 * sizeof(uint64_t), s0));
+    if (e->temp_cnt) HIP_TRY(hipMemsetAsync(e->temp_cnt, 0, 2 * sizeof(uint64_t), s0));
     HIP_TRY(hipStreamSynchronize(s0));
     if (cfg->evaluator == OAZ_EVAL_NN) {  // random-init weights until oaz_load_weights
         std::vector<float> w(oaz_weight_count(cfg->blocks, 64, 21));
@@ -1237,7 +1247,7 @@ extern "C" int oaz_search_resume(oaz_engine* e, int G, oaz_move* out_move, float
 int oaz_engine_reuse_view(oaz_engine* e, oaz_reuse_engine_view* out) {
     if (!e || !out) return oaz_set_err(OAZ_ERR_ARG, "tree reuse: null engine");
     *out = {e->device, e->searched, e->cap, e->cfg.reuse_visits, e->sims_cap, e->nodes, e->n_nodes, e->s_roots,
-            e->adv_moves, e->adv_codes, e->adv_kept, e->reuse_cnt, e->stream};
+            e->adv_moves, e->adv_codes, e->adv_kept, e->reuse_cnt, e->stream, e->cfg.seed};
     return 0;
 }
 int oaz_engine_reuse_advanced(oaz_engine* e, int G, int32_t most) {
@@ -1270,6 +1280,7 @@ extern "C" int oaz_selfplay_reset(oaz_engine* e) {
     HIP_TRY(hipMemsetAsync(e->out_count, 0, sizeof(unsigned long long), e->stream));
     e->out_read = 0;
     if (e->reuse_cnt) HIP_TRY(hipMemsetAsync(e->reuse_cnt, 0, 4 * sizeof(uint64_t), e->stream));
+    if (e->temp_cnt) HIP_TRY(hipMemsetAsync(e->temp_cnt, 0, 2 * sizeof(uint64_t), e->stream));
     e->ply_trees = false;
     e->searched = 0;
     HIP_TRY(launch_selfplay_reset(t, slot_view(e), e->stream));
@@ -1285,6 +1296,7 @@ extern "C" int oaz_selfplay_step(oaz_engine* e, int moves) {
     OAZ_ON_DEVICE(e->device);
     const TreeView t = tree_view(e, e->G);
     const SlotView sv = slot_view(e);
+    const uint32_t temp_plies = e->cfg.temperature_plies;  // 0: the launches of an engine without temperature
     for (int m = 0; m < moves; ++m) {
         if (int rc = begin_budget(e)) return rc;
         const bool reuse = e->cfg.reuse_visits > 0;
@@ -1292,10 +1304,15 @@ extern "C" int oaz_selfplay_step(oaz_engine* e, int moves) {
         if (!reuse)
             HIP_TRY(launch_tree_reset(t, e->stream));  // a fresh tree per move (the last ply's stays dumpable)
         else  // tree reuse: the played move's subtree where the keep rule holds, a fresh root elsewhere
-            HIP_TRY(launch_selfplay_rebase(t, sv, e->ply_trees, e->sims_cap, e->cfg.reuse_visits, e->reuse_cnt, e->stream));
+            HIP_TRY(launch_selfplay_rebase(t, sv, e->ply_trees, e->sims_cap, e->cfg.reuse_visits, temp_plies, e->reuse_cnt,
+                                           e->stream));
         e->ply_trees = false;
         if (int rc = run_sims(e, t, e->root, e->active, e->game_id, e->ply, reuse)) return rc;
-        if (int rc = timed(e, K_FINALIZE, e->G, [&] { return launch_selfplay_move(t, sv, e->stream); })) return rc;
+        if (int rc = timed(e, K_FINALIZE, e->G, [&] {
+                return temp_plies ? launch_selfplay_move_temp(t, sv, temp_plies, e->temp_cnt, e->stream)
+                                  : launch_selfplay_move(t, sv, e->stream);
+            }))
+            return rc;
         e->ply_trees = true;
     }
     return 0;
@@ -1341,6 +1358,16 @@ extern "C" int oaz_selfplay_stats_get(oaz_engine* e, oaz_selfplay_stats* o) {
     o->samples_dropped = s[GS_DROPPED];
     o->samples_ready = ready;
     fill_search_stats(s, &o->search);
+    return 0;
+}
+
+extern "C" int oaz_selfplay_temperature_stats(oaz_engine* e, uint64_t out[2]) {
+    if (!e || !out) return oaz_set_err(OAZ_ERR_ARG, "selfplay_temperature_stats: null");
+    out[0] = out[1] = 0;
+    if (!e->temp_cnt) return 0;
+    OAZ_ON_DEVICE(e->device);
+    HIP_TRY(hipMemcpyAsync(out, e->temp_cnt, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;
 }
 

@@ -199,6 +199,7 @@ struct oaz_reuse_engine_view {
     int32_t *codes, *kept;
     uint64_t* counters;
     hipStream_t stream;
+    uint64_t seed;  // cfg.seed (oaz_search_sample_moves)
 };
 int oaz_engine_reuse_view(oaz_engine* e, oaz_reuse_engine_view* out);
 int oaz_engine_reuse_advanced(oaz_engine* e, int G, int32_t most);

@@ -163,7 +163,15 @@ hipError_t launch_stats_reduce(const uint64_t* per_game, uint32_t G, uint64_t* o
 // other slot gets a fresh root; prev = the trees are the previous ply's. counters: the oaz_reuse_stats fields.
 // A weak declaration: the engine's host code also links without oaz_tree_reuse.hip (a host-only build with
 // stand-in launchers), where an engine with reuse_visits > 0 cannot be made.
+// temp_plies = oaz_config.temperature_plies: where the previous ply drew its move, the kept subtree is the drawn
+// child's (0: the kernel of an engine without temperature).
 __attribute__((weak)) hipError_t launch_selfplay_rebase(const TreeView& t, const SlotView& s, int prev, int32_t sims_cap,
-                                                        int32_t R, uint64_t* counters, hipStream_t st);
+                                                        int32_t R, uint32_t temp_plies, uint64_t* counters,
+                                                        hipStream_t st);
+// Self-play temperature (temperature_plies = temp_plies > 0), in place of launch_selfplay_move: in a game's first
+// temp_plies plies the played move is drawn from the root visits (temperature_draw_child, oaz_device.h). counters: the
+// two of oaz_selfplay_temperature_stats. Weak for the same reason: such an engine cannot be made without it.
+__attribute__((weak)) hipError_t launch_selfplay_move_temp(const TreeView& t, const SlotView& s, uint32_t temp_plies,
+                                                           uint64_t* counters, hipStream_t st);
 
 }  // namespace oaz

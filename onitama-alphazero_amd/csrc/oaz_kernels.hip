@@ -1214,6 +1214,35 @@ __device__ __forceinline__ void root_pi_best(const oaz_node* T, float* pi_out /*
     K_out = K;
 }
 
+// temperature_draw_child (oaz_device.h) on a wave: lane l holds child l's visits n (0 in the lanes from K on; K <= 40).
+// The inclusive prefix sum runs over all 64 lanes, lane 63 holds S, and the first lane whose sum exceeds r is the
+// child: the lanes from K on hold S > r, so a first lane always exists and lies below K. Returns the child
+// (wave-uniform), or -1 without a visit.
+__device__ __forceinline__ int wave_temperature_pick(uint64_t seed, uint64_t game, uint32_t ply, uint32_t n) {
+    const uint32_t incl = wave_incl_scan(n);
+    const uint32_t S = (uint32_t)__shfl((int)incl, 63);
+    if (S == 0) return -1;
+    const uint32_t r = temperature_draw(seed, game, ply, S);
+    return __ffsll((unsigned long long)__ballot(incl > r)) - 1;
+}
+
+// The child of T's root that the temperature rule draws for (game, ply), and its packed move; -1 without a child
+// or a visit (no draw). The caller has checked ply < temperature_plies.
+__device__ __forceinline__ int root_temperature_child(const oaz_node* T, uint64_t seed, uint64_t game, uint32_t ply,
+                                                      uint32_t& mv) {
+    const int l = lane_id();
+    const NodeRegs root = load_node(&T[0]);
+    const int K = (node_flags(root.misc) & 1) ? node_nch(root.misc) : 0;
+    if (K == 0) return -1;
+    NodeRegs ch;
+    ch.N = 0;
+    ch.misc = 0;
+    if (l < K) ch = load_node(&T[root.first + l]);
+    const int c = wave_temperature_pick(seed, game, ply, ch.N);
+    if (c >= 0) mv = (uint32_t)__shfl((int)ch.misc, c) & 0xFFFFu;
+    return c;
+}
+
 __global__ void __launch_bounds__(kBlock) k_search_finalize(TreeView t, const oaz_state* __restrict__ roots,
                                                             oaz_move* out_move, float* out_pi) {
     const uint32_t g = wave_game();
@@ -1270,12 +1299,20 @@ __global__ void __launch_bounds__(kBlock) k_selfplay_reset(TreeView t, SlotView 
     t.n_nodes[g] = 1;
 }
 
+// Counters of oaz_selfplay_temperature_stats, in its order.
+enum TemperatureStat { TS_DRAWS = 0, TS_DIFFER, TS_COUNT };
+
 // One ply of self_play (train.rs:55-80) per slot: record (state, pi, colour), play the most
-// visited move (no temperature, Q9), detect the end (win, or the 152-ply cut of
+// visited move (the reference has no temperature, Q9), detect the end (win, or the 152-ply cut of
 // train.rs:74-79), emit z = reward(result, colour) for every sample (train.rs:83-85) and deal the
 // next game. The tree is reset before the next ply's search (oaz_selfplay_step: k_tree_reset, a fresh
 // tree per move, alphazero_mcts/mod.rs:68-77), so the ply's tree can be dumped in between.
-__global__ void __launch_bounds__(kBlock) k_selfplay_move(TreeView t, SlotView sv) {
+// kTemp (oaz_config.temperature_plies = temp_plies > 0, k_selfplay_move_temp): in a game's first temp_plies plies
+// the played move is the child temperature_draw_child draws from the visits instead; the recorded pi is the visit
+// distribution either way. cnt counts the plies that drew and the draws that differ from the most visited child.
+template <bool kTemp>
+__device__ __forceinline__ void selfplay_move_body(const TreeView& t, const SlotView& sv, uint32_t temp_plies,
+                                                   unsigned long long* cnt) {
     const uint32_t g = wave_game();
     if (g >= t.G) return;
     const uint8_t act = sv.active[g];
@@ -1297,6 +1334,17 @@ __global__ void __launch_bounds__(kBlock) k_selfplay_move(TreeView t, SlotView s
     uint32_t mv;
     const uint32_t hslot = ply < sv.hcap ? ply : sv.hcap - 1;
     root_pi_best(T, hist[hslot].pi, pl, best, K, mv);
+    if (kTemp && K > 0 && ply < temp_plies) {  // (wave-uniform)
+        uint32_t drawn_mv = 0;
+        const int c = root_temperature_child(T, sv.seed, sv.game_id[g], ply, drawn_mv);
+        if (c >= 0) {
+            if (l == 0) {
+                atomicAdd(&cnt[TS_DRAWS], 1ull);
+                if (c != best) atomicAdd(&cnt[TS_DIFFER], 1ull);
+            }
+            mv = drawn_mv;
+        }
+    }
     if (l == 0) {
         store_state(&hist[hslot].state, s);
         hist[hslot].z = 0.0f;
@@ -1335,6 +1383,14 @@ __global__ void __launch_bounds__(kBlock) k_selfplay_move(TreeView t, SlotView s
         sv.fin[g] = 0u;
     }
     // the tree stays as searched (oaz_tree_dump after a ply); the next ply starts from k_tree_reset
+}
+
+__global__ void __launch_bounds__(kBlock) k_selfplay_move(TreeView t, SlotView sv) {
+    selfplay_move_body<false>(t, sv, 0u, nullptr);
+}
+__global__ void __launch_bounds__(kBlock) k_selfplay_move_temp(TreeView t, SlotView sv, uint32_t temp_plies,
+                                                               unsigned long long* cnt) {
+    selfplay_move_body<true>(t, sv, temp_plies, cnt);
 }
 
 // The records of the games that ended in this ply, in slot order (the reference appends a worker's
@@ -1508,6 +1564,15 @@ hipError_t launch_selfplay_move(const TreeView& t, const SlotView& s, hipStream_
     hipLaunchKernelGGL(k_samples_emit, dim3(wave_grid(t.G)), dim3(kBlock), 0, st, t, s);
     return hipGetLastError();
 }
+hipError_t launch_selfplay_move_temp(const TreeView& t, const SlotView& s, uint32_t temp_plies, uint64_t* counters,
+                                     hipStream_t st) {
+    hipLaunchKernelGGL(k_selfplay_move_temp, dim3(wave_grid(t.G)), dim3(kBlock), 0, st, t, s, temp_plies,
+                       reinterpret_cast<unsigned long long*>(counters));
+    hipLaunchKernelGGL(k_samples_scan, dim3(1), dim3(kScanThreads), 0, st, s);
+    hipLaunchKernelGGL(k_samples_emit, dim3(wave_grid(t.G)), dim3(kBlock), 0, st, t, s);
+    return hipGetLastError();
+}
+
 hipError_t launch_selfplay_reset(const TreeView& t, const SlotView& s, hipStream_t st) {
     hipLaunchKernelGGL(k_selfplay_reset, dim3(thread_grid(t.G, kBlock)), dim3(kBlock), 0, st, t, s);
     return hipGetLastError();

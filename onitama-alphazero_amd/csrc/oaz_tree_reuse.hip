@@ -3,6 +3,8 @@
 // oaz_tree_rebase.h, one wave per game as the other tree kernels); k_selfplay_rebase applies it between two
 // self-play plies in place of k_tree_reset, k_tree_advance for oaz_search_advance. Part of the oaz_gpu.hip
 // translation unit (after oaz_kernels.hip, whose device helpers it uses); it changes no other kernel.
+// Also here, as the other entry point that reads the trees of the last search: oaz_search_sample_moves
+// (k_sample_moves), the self-play temperature rule's draw for a caller that plays its own games.
 #include <string.h>
 
 #include <vector>
@@ -139,8 +141,11 @@ __device__ __forceinline__ void next_tree(const TreeView& t, uint32_t g, bool ke
 // (active, ply > 0, and `prev`: the trees are that ply's) keeps the subtree of the move k_selfplay_move played,
 // root_pi_best's last maximum of N, when the keep rule holds; a won game has ended (ply 0). Every other slot
 // (a new game, a staggered start, an inactive slot, a pass) gets a fresh root.
+// kTemp (temperature_plies = temp_plies > 0): where the previous ply drew its move (ply - 1 < temp_plies), the
+// played child is that draw, recomputed from (seed, game id, ply - 1) on the same tree, not the last maximum.
+template <bool kTemp>
 __global__ void __launch_bounds__(kBlock) k_selfplay_rebase(TreeView t, SlotView sv, int prev, int32_t sims_cap,
-                                                            int32_t R, unsigned long long* cnt) {
+                                                            int32_t R, uint32_t temp_plies, unsigned long long* cnt) {
     const uint32_t g = wave_game();
     if (g >= t.G) return;
     const oaz_node* T = t.nodes + (size_t)g * t.cap;
@@ -153,6 +158,10 @@ __global__ void __launch_bounds__(kBlock) k_selfplay_rebase(TreeView t, SlotView
         int best, K;
         uint32_t mv;
         root_pi_best(T, nullptr, pl, best, K, mv);
+        if (kTemp && K > 0 && sv.ply[g] - 1 < temp_plies) {  // (wave-uniform)
+            const int drawn = root_temperature_child(T, sv.seed, sv.game_id[g], sv.ply[g] - 1, mv);
+            if (drawn >= 0) best = drawn;
+        }
         if (K > 0) {
             const NodeRegs root = load_node(&T[0]);
             c = root.first + (uint32_t)best;
@@ -227,10 +236,55 @@ __global__ void __launch_bounds__(kBlock) k_tree_advance(TreeView t, oaz_state* 
 }
 
 hipError_t launch_selfplay_rebase(const TreeView& t, const SlotView& s, int prev, int32_t sims_cap, int32_t R,
-                                  uint64_t* counters, hipStream_t st) {
-    hipLaunchKernelGGL(k_selfplay_rebase, dim3(wave_grid(t.G)), dim3(kBlock), 0, st, t, s, prev, sims_cap, R,
-                       reinterpret_cast<unsigned long long*>(counters));
+                                  uint32_t temp_plies, uint64_t* counters, hipStream_t st) {
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counters);
+    if (temp_plies == 0)
+        hipLaunchKernelGGL(k_selfplay_rebase<false>, dim3(wave_grid(t.G)), dim3(kBlock), 0, st, t, s, prev, sims_cap, R,
+                           0u, cnt);
+    else
+        hipLaunchKernelGGL(k_selfplay_rebase<true>, dim3(wave_grid(t.G)), dim3(kBlock), 0, st, t, s, prev, sims_cap, R,
+                           temp_plies, cnt);
     return hipGetLastError();
+}
+
+// oaz_search_sample_moves: the move the temperature rule draws from game g's resident tree for (gids[g], plies[g]):
+// the drawn child, the last maximum of the visits where no child has a visit, the pass of k_search_finalize (child
+// -1) at a root without a child.
+__global__ void __launch_bounds__(kBlock) k_sample_moves(TreeView t, const oaz_state* __restrict__ roots, uint64_t seed,
+                                                         const uint64_t* __restrict__ gids,
+                                                         const uint32_t* __restrict__ plies, oaz_move* out_moves,
+                                                         int32_t* out_child) {
+    const uint32_t g = wave_game();
+    if (g >= t.G) return;
+    const oaz_node* T = t.nodes + (size_t)g * t.cap;
+    float pl;
+    int best, K;
+    uint32_t mv;
+    root_pi_best(T, nullptr, pl, best, K, mv);
+    if (K > 0) {
+        uint32_t drawn_mv = 0;
+        const int c = root_temperature_child(T, seed, gids[g], plies[g], drawn_mv);
+        if (c >= 0) {
+            best = c;
+            mv = drawn_mv;
+        }
+    }
+    if (lane_id() == 0) {
+        oaz_move m;
+        if (K == 0) {  // no legal move (Q6): pass with the mover's first card
+            m.from = 25;
+            m.to = 25;
+            m.piece = 0;
+            m.slot = (uint8_t)((roots[g].to_move & 1) ? 2 : 0);
+        } else {
+            m.from = (uint8_t)mv_from(mv);
+            m.to = (uint8_t)mv_to(mv);
+            m.piece = (uint8_t)mv_piece(mv);
+            m.slot = (uint8_t)mv_slot(mv);
+        }
+        out_moves[g] = m;
+        out_child[g] = K == 0 ? -1 : best;
+    }
 }
 
 }  // namespace oaz
@@ -278,6 +332,37 @@ extern "C" int oaz_search_advance(oaz_engine* e, const oaz_move* moves, int G, i
         if (kept) kept[g] = h[(size_t)g];
     }
     return oaz_engine_reuse_advanced(e, G, most);
+}
+
+extern "C" int oaz_search_sample_moves(oaz_engine* e, int G, const uint64_t* game_ids, const uint32_t* plies,
+                                       oaz_move* out_moves, int32_t* out_child) {
+    oaz_reuse_engine_view v;
+    if (int rc = oaz_engine_reuse_view(e, &v)) return rc;
+    if (G < 0 || !game_ids || !plies || (!out_moves && !out_child))
+        return oaz_set_err(OAZ_ERR_ARG, "search_sample_moves: bad arguments");
+    if ((uint32_t)G > v.searched)
+        return oaz_set_err(OAZ_ERR_STATE, "search_sample_moves: G=%d, but the trees of %u games are the last search's", G,
+                           v.searched);
+    if (G == 0) return 0;
+    OAZ_ON_DEVICE(v.device);
+    // per-call scratch (freed on return, after the stream is done with it): a driver's call per ply, not a hot path
+    DevBuf<uint64_t> d_gid;
+    DevBuf<uint32_t> d_ply;
+    DevBuf<oaz_move> d_mv;
+    DevBuf<int32_t> d_child;
+    if (d_gid.alloc((size_t)G) || d_ply.alloc((size_t)G) || d_mv.alloc((size_t)G) || d_child.alloc((size_t)G)) return OAZ_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(d_gid, game_ids, (size_t)G * 8, hipMemcpyHostToDevice, v.stream));
+    HIP_TRY(hipMemcpyAsync(d_ply, plies, (size_t)G * 4, hipMemcpyHostToDevice, v.stream));
+    hipLaunchKernelGGL(k_sample_moves, dim3(wave_grid((uint32_t)G)), dim3(kBlock), 0, v.stream,
+                       reuse_tree_view(v, (uint32_t)G), v.roots, v.seed, d_gid.get(), d_ply.get(), d_mv.get(), d_child.get());
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess && out_moves)
+        err = hipMemcpyAsync(out_moves, d_mv, (size_t)G * sizeof(oaz_move), hipMemcpyDeviceToHost, v.stream);
+    if (err == hipSuccess && out_child) err = hipMemcpyAsync(out_child, d_child, (size_t)G * 4, hipMemcpyDeviceToHost, v.stream);
+    const hipError_t done = hipStreamSynchronize(v.stream);  // before the scratch is freed, whatever happened
+    HIP_TRY(err);
+    HIP_TRY(done);
+    return 0;
 }
 
 extern "C" int oaz_reuse_stats_get(oaz_engine* e, oaz_reuse_stats* out) {

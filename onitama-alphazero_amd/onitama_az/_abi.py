@@ -79,7 +79,8 @@ class oaz_config(C.Structure):
         ("precision", C.c_int32),
         ("fixed_deck", C.c_int32),
         ("deck", C.c_uint8 * 5),
-        ("pad0", C.c_uint8 * 3),
+        ("temperature_plies", C.c_uint8),
+        ("pad0", C.c_uint8 * 2),
         ("seed", C.c_uint64),
         ("rank", C.c_int32),
         ("world", C.c_int32),
@@ -286,6 +287,7 @@ assert C.sizeof(oaz_node) == 32
 assert C.sizeof(oaz_sample) == 228
 assert C.sizeof(oaz_config) == 120 and oaz_config.search_time_ns.offset == 104
 assert oaz_config.reuse_visits.offset == 116 and C.sizeof(oaz_reuse_stats) == 32
+assert oaz_config.temperature_plies.offset == 69 and oaz_config.seed.offset == 72
 assert C.sizeof(oaz_arena_agent) == 88 and C.sizeof(oaz_arena_config) == 40 and C.sizeof(oaz_fight_stats) == 96
 assert C.sizeof(oaz_arena_slots_stats) == 40
 
@@ -323,6 +325,7 @@ _PROTOS = {
     "oaz_slot_game_ids": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, _VOIDP]),
     "oaz_hash_eval": (None, [_VOIDP, _VOIDP, _VOIDP]),
     "oaz_root_noise": (C.c_double, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int]),
+    "oaz_temperature_pick": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, _VOIDP, C.c_int]),
     "oaz_movegen": (C.c_int, [_VOIDP, C.c_int, _VOIDP, _VOIDP, _VOIDP]),
     "oaz_step": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _VOIDP]),
     "oaz_current_state": (C.c_int, [_VOIDP, C.c_int, _VOIDP]),
@@ -355,9 +358,11 @@ _PROTOS = {
     "oaz_search_resume": (C.c_int, [_VOIDP, C.c_int, _VOIDP, _VOIDP, _VOIDP, _P(oaz_search_stats), _VOIDP]),
     "oaz_reuse_stats_get": (C.c_int, [_VOIDP, _P(oaz_reuse_stats)]),
     "oaz_tree_rebase_host": (C.c_int, [_VOIDP, C.c_int, C.c_int, _VOIDP, C.c_int, _P(C.c_int)]),
+    "oaz_search_sample_moves": (C.c_int, [_VOIDP, C.c_int, _VOIDP, _VOIDP, _VOIDP, _VOIDP]),
     "oaz_selfplay_reset": (C.c_int, [_VOIDP]),
     "oaz_selfplay_step": (C.c_int, [_VOIDP, C.c_int]),
     "oaz_selfplay_stats_get": (C.c_int, [_VOIDP, _P(oaz_selfplay_stats)]),
+    "oaz_selfplay_temperature_stats": (C.c_int, [_VOIDP, _P(C.c_uint64 * 2)]),
     "oaz_samples_fetch": (C.c_int, [_VOIDP, _VOIDP, C.c_size_t, _P(C.c_size_t)]),
     "oaz_samples_export_device": (C.c_int, [_VOIDP, _VOIDP, C.c_size_t, _P(C.c_size_t)]),
     "oaz_selfplay_run": (C.c_int, [_VOIDP, C.c_int, _VOIDP, C.c_size_t, _P(C.c_size_t), _P(oaz_selfplay_stats)]),

@@ -154,6 +154,28 @@ class Engine:
         _abi.check(self._lib.oaz_reuse_stats_get(self._h, C.byref(st)))
         return st
 
+    # -- self-play temperature (Engine(temperature_plies=T): a game's first T plies draw the move from the visits) --
+    def sample_moves(self, game_ids, plies) -> Tuple[np.ndarray, np.ndarray]:
+        """After search() / resume(): (moves [G] MOVE_DTYPE, child [G] int32) the temperature rule draws from
+        game g's tree for (game_ids[g], plies[g]) under the engine's seed, whatever temperature_plies is: the
+        drawn child, the most visited one where no child has a visit, the pass move and child -1 without a child."""
+        game_ids = np.ascontiguousarray(game_ids, dtype=np.uint64)
+        plies = np.ascontiguousarray(plies, dtype=np.uint32)
+        if game_ids.shape != plies.shape or game_ids.ndim != 1:
+            raise ValueError("sample_moves: game_ids and plies are two 1-d arrays of one length")
+        moves = np.zeros(len(game_ids), dtype=_abi.MOVE_DTYPE)
+        child = np.zeros(len(game_ids), dtype=np.int32)
+        _abi.check(self._lib.oaz_search_sample_moves(self._h, len(game_ids), _abi.ptr(game_ids), _abi.ptr(plies),
+                                                     _abi.ptr(moves), _abi.ptr(child)))
+        return moves, child
+
+    def temperature_stats(self) -> Tuple[int, int]:
+        """(self-play plies whose move was drawn, draws whose child is not the most visited one) since
+        selfplay_reset()."""
+        out = (C.c_uint64 * 2)()
+        _abi.check(self._lib.oaz_selfplay_temperature_stats(self._h, C.byref(out)))
+        return int(out[0]), int(out[1])
+
     # -- self-play --
     def selfplay_reset(self) -> None:
         _abi.check(self._lib.oaz_selfplay_reset(self._h))

@@ -53,6 +53,9 @@ class LoopConfig:  # TrainConfig, train.rs:100-154 (defaults of Default::default
     evaluator_config: EvaluatorConfig = field(default_factory=EvaluatorConfig)
     seed: int = 20260101
     reuse_visits: int = 0  # self-play tree reuse (oaz_config.reuse_visits): 0 = a fresh tree per ply, as the reference
+    # self-play temperature (oaz_config.temperature_plies): a game's first T plies draw the move in proportion to the
+    # root visits; 0 = always the most visited move, as the reference (Q9). The pit and the arena never draw.
+    temperature_plies: int = 0
 
 
 @dataclass
@@ -110,7 +113,8 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
             kw = dict(games=max(1, min(per_rank, 65536)), sims=mc.max_playouts, c_puct=mc.exploration_c,
                       train_noise=int(mc.train), blocks=blocks, max_plies=config.max_plies, evaluator=_abi.EVAL_NN,
                       precision=options.precision, seed=config.seed + it, rank=rank, world=world,
-                      sample_capacity=max(1, per_rank) * (config.max_plies + 2), reuse_visits=config.reuse_visits)
+                      sample_capacity=max(1, per_rank) * (config.max_plies + 2), reuse_visits=config.reuse_visits,
+                      temperature_plies=config.temperature_plies)
             if config.deck is not None:
                 kw.update(fixed_deck=1, deck=config.deck.indices())
             with Engine(device=options.device, **kw) as eng:
