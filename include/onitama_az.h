@@ -128,7 +128,8 @@ typedef struct oaz_node {
     uint16_t mv;     /* packed move: from | to<<5 | slot<<10 | piece<<12 */
     uint8_t nch;     /* number of children */
     uint8_t flags;   /* bit0 expanded, bit1 terminal */
-    uint32_t pad;    /* 0. With tree reuse the re-rooting kernel uses this word as its scratch while it runs and
+    uint32_t pad;    /* 0. The leaf-parallel search (oaz_config.leaf_batch) keeps a node's in-flight count here
+                      * during a round and leaves 0 after every round. With tree reuse the re-rooting kernel uses this word as its scratch while it runs and
                       * leaves 0 again in every node; only a tree dumped after that kernel was cut short (a
                       * failed launch, a reset device) can show other values here */
 } oaz_node; /* 32 bytes */
@@ -163,7 +164,18 @@ typedef struct oaz_config {
                                 by seed, game id and ply: oaz_temperature_pick); later plies play the most
                                 visited move. The recorded pi is the visit distribution either way. Self-play
                                 only: oaz_search, the arena and the Agent API ignore it */
-    uint8_t pad0[2];
+    uint8_t leaf_batch;      /* leaf-parallel search (DESIGN.md "Leaf-parallel search"): 0 = off (default, and what a
+                                zeroed pad byte of an older caller means): the searches, memory and launches of an
+                                engine without the feature. L = 1 .. 16: oaz_search and the arena's resident search
+                                of at most CU-count roots collect up to L leaves of a root's tree per network pass
+                                (virtual loss: every node has an in-flight count, oaz_node.pad, 0 outside a round)
+                                and evaluate them as one 16-position tile, one launch for the whole search. L = 1
+                                is the sequential search bit for bit; from L + 1 playouts on the trees differ from
+                                it, by the rule stated in DESIGN.md. Needs step_kernels = 0, compact = 0,
+                                reuse_visits = 0 and the fp16x3 network or HASH (checked at creation); a search
+                                with root noise or more roots than CUs, and self-play, fail with OAZ_ERR_STATE:
+                                there is no fallback to another algorithm. Values above 16 are rejected */
+    uint8_t pad0[1];
     uint64_t seed;           /* counter-based RNG key for deals, Dirichlet noise and temperature draws */
     int32_t rank;            /* global game id = (k * world + rank) * games + slot */
     int32_t world;
@@ -327,6 +339,10 @@ int oaz_last_sims(oaz_engine* eng, int* sims);
 /* Playouts each of the first G games of the last search / ply ran (the reference's
  * MctsArena.playouts after search(), mcts_arena.rs:75-81); G <= the last call's games. */
 int oaz_search_playouts(oaz_engine* eng, int* out, int G);
+/* Leaf-parallel search (oaz_config.leaf_batch > 0): out[0] = rounds (network passes), out[1] = playouts and
+ * out[2] = discarded walks (a walk that reached a leaf already in flight closes its round and counts no playout)
+ * of the last search, summed over its roots. All 0 with leaf_batch == 0 or before the first search. */
+int oaz_search_leaf_batch_stats(oaz_engine* eng, uint64_t out[3]);
 /* Weights in canonical order (n == oaz_weight_count). BN is folded on the host. */
 int oaz_load_weights(oaz_engine* eng, const float* blob, size_t n);
 

@@ -31,6 +31,8 @@ using namespace oaz;
 static_assert(offsetof(oaz_config, search_time_ns) == 104 && offsetof(oaz_config, reuse_visits) == 116 &&
                   sizeof(oaz_config) == 120,
               "oaz_config layout (ABI 4; reuse_visits took the reserved word)");
+static_assert(offsetof(oaz_config, leaf_batch) == 70 && offsetof(oaz_config, seed) == 72,
+              "oaz_config layout (leaf_batch took a pad byte)");
 
 // ---- errors ---------------------------------------------------------------------------------
 static thread_local std::string g_err;
@@ -337,6 +339,13 @@ struct oaz_engine {
     DevBuf<oaz_move> adv_moves;
     DevBuf<int32_t> adv_codes, adv_kept;
     DevBuf<uint64_t> reuse_cnt;
+    // leaf-parallel search (cfg.leaf_batch > 0; nothing is allocated without it): the rounds' records per root
+    // (ParBufs, oaz_kernels.h)
+    DevBuf<uint32_t> par_path, par_depth, par_leaf;
+    DevBuf<oaz_state> par_state;
+    DevBuf<float> par_policy, par_value;
+    DevBuf<uint64_t> par_stats;
+    uint32_t par_G = 0;           // roots of the last leaf-parallel search (0: none yet)
     DevBuf<uint64_t> temp_cnt;    // self-play temperature (cfg.temperature_plies > 0 only): oaz_selfplay_temperature_stats
     uint32_t searched = 0;        // games whose trees are the last oaz_search / oaz_search_resume's (0: self-play ran since)
     int64_t tree_visits = 0;      // the most root visits any of those trees can hold by now
@@ -510,6 +519,7 @@ static int timed(oaz_engine* e, LaunchKind kind, uint32_t samples, F&& launch, h
 static uint32_t tree_visits_cap(const oaz_config* cfg) {
     return (uint32_t)(cfg->reuse_visits > 0 ? cfg->reuse_visits : cfg->sims);
 }
+constexpr int kMaxLeafBatch = 16;  // oaz_config.leaf_batch: the leaves of a round are one network tile
 constexpr int32_t kMaxReuseVisits = 1 << 20;  // 1 + R * OAZ_MAX_MOVES nodes fit 32-bit node indices with room
 
 static int create_check(const oaz_config* cfg, int device) {
@@ -535,6 +545,19 @@ static int create_check(const oaz_config* cfg, int device) {
     if (cfg->precision != OAZ_FP32 && cfg->precision != OAZ_BF16 && cfg->precision != OAZ_FP32_SPLIT &&
         cfg->precision != OAZ_FP32_SPLIT16)
         return oaz_set_err(OAZ_ERR_ARG, "create: precision must be OAZ_FP32, OAZ_BF16, OAZ_FP32_SPLIT or OAZ_FP32_SPLIT16");
+    if (cfg->leaf_batch > kMaxLeafBatch)
+        return oaz_set_err(OAZ_ERR_ARG, "create: leaf_batch=%d > %d (one 16-position tile)", cfg->leaf_batch, kMaxLeafBatch);
+    if (cfg->leaf_batch > 0) {  // the combinations that could never run the leaf-parallel search: no other algorithm
+        if (!launch_search_par)
+            return oaz_set_err(OAZ_ERR_ARG, "create: leaf_batch > 0 in a build without the leaf-parallel search kernel");
+        if (cfg->step_kernels == 1)
+            return oaz_set_err(OAZ_ERR_ARG, "create: leaf_batch > 0 needs step_kernels = 0 (it is a one-launch search)");
+        if (cfg->compact != 0) return oaz_set_err(OAZ_ERR_ARG, "create: leaf_batch > 0 needs compact = 0");
+        if (cfg->evaluator != OAZ_EVAL_HASH && cfg->precision != OAZ_FP32_SPLIT16)
+            return oaz_set_err(OAZ_ERR_ARG, "create: leaf_batch > 0 needs the fp16x3 network (OAZ_FP32_SPLIT16) or HASH");
+        if (cfg->reuse_visits > 0)
+            return oaz_set_err(OAZ_ERR_ARG, "create: leaf_batch > 0 and reuse_visits > 0 (tree reuse) do not combine");
+    }
     return oaz_check_device("create", device);
 }
 
@@ -571,6 +594,12 @@ static int engine_init(oaz_engine* e) {
         (e->adv_moves.alloc(G) || e->adv_codes.alloc(G) || e->adv_kept.alloc(G) || e->reuse_cnt.alloc(4)))
         return OAZ_ERR_HIP;
     if (cfg->temperature_plies > 0 && e->temp_cnt.alloc(2)) return OAZ_ERR_HIP;
+    if (const size_t L = cfg->leaf_batch) {
+        if (e->par_path.alloc(G * L * e->pathcap) || e->par_depth.alloc(G * L) || e->par_leaf.alloc(G * L) ||
+            e->par_state.alloc(G * kMaxLeafBatch) || e->par_policy.alloc(G * kMaxLeafBatch * 50) ||
+            e->par_value.alloc(G * kMaxLeafBatch) || e->par_stats.alloc(G * 3))
+            return OAZ_ERR_HIP;
+    }
     // sqrt((double)n) from the host libm (IEEE correctly rounded), so device PUCT = oracle PUCT
     std::vector<double> tab((size_t)tree_visits_cap(cfg) + 2);
     for (size_t i = 0; i < tab.size(); ++i) tab[i] = sqrt((double)i);
@@ -588,6 +617,10 @@ static int engine_init(oaz_engine* e) {
     HIP_TRY(hipMemsetAsync(e->cstate, 0, (G + 16) * sizeof(oaz_state), s0));
     if (e->reuse_cnt) HIP_TRY(hipMemsetAsync(e->reuse_cnt, 0, 4 * sizeof(uint64_t), s0));
     if (e->temp_cnt) HIP_TRY(hipMemsetAsync(e->temp_cnt, 0, 2 * sizeof(uint64_t), s0));
+    if (e->par_state) {
+        HIP_TRY(hipMemsetAsync(e->par_state, 0, G * kMaxLeafBatch * sizeof(oaz_state), s0));
+        HIP_TRY(hipMemsetAsync(e->par_stats, 0, G * 3 * sizeof(uint64_t), s0));
+    }
     HIP_TRY(hipStreamSynchronize(s0));
     if (cfg->evaluator == OAZ_EVAL_NN) {  // random-init weights until oaz_load_weights
         std::vector<float> w(oaz_weight_count(cfg->blocks, 64, 21));
@@ -681,6 +714,18 @@ extern "C" int oaz_search_playouts(oaz_engine* e, int* out, int G) {
         return oaz_set_err(OAZ_ERR_ARG, "search_playouts: G=%d > %u games in the last search", G, e->last.G);
     if (int rc = fetch_sims_run(e)) return rc;
     for (int g = 0; g < G; ++g) out[g] = (int)(e->last.per_game.empty() ? e->last.sims : e->last.per_game[(size_t)g]);
+    return 0;
+}
+
+extern "C" int oaz_search_leaf_batch_stats(oaz_engine* e, uint64_t out[3]) {
+    if (!e || !out) return oaz_set_err(OAZ_ERR_ARG, "search_leaf_batch_stats: null");
+    out[0] = out[1] = out[2] = 0;
+    if (e->cfg.leaf_batch == 0 || e->par_G == 0) return 0;
+    OAZ_ON_DEVICE(e->device);
+    std::vector<uint64_t> v((size_t)e->par_G * 3);
+    HIP_TRY(hipMemcpyAsync(v.data(), e->par_stats, v.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t i = 0; i < v.size(); ++i) out[i % 3] += v[i];
     return 0;
 }
 
@@ -810,8 +855,11 @@ static bool compact_leaves(const oaz_engine* e, uint32_t G) {
 //   GRP    k_search_grp: 16 games per workgroup, up to one round of workgroups, one launch per root-noise
 //          chunk (any G below a qualifying engine's qualifies as well);
 //   STEPS  the per-simulation-step launches; always so for a search that goes on with kept trees (tree reuse).
-enum SearchPath { PATH_LAT, PATH_GRP, PATH_STEPS };
+//   PAR    k_search_par: an engine with leaf_batch > 0, every search it accepts (par_search_check refuses the
+//          others; create_check the configurations that never could).
+enum SearchPath { PATH_LAT, PATH_GRP, PATH_STEPS, PATH_PAR };
 static SearchPath search_path(const oaz_engine* e, uint32_t G, bool noise, bool kept_trees = false) {
+    if (e->cfg.leaf_batch > 0) return PATH_PAR;
     const bool one_launch = !kept_trees && e->cfg.step_kernels == 0 && !compact_leaves(e, G) &&
                             (e->cfg.evaluator == OAZ_EVAL_HASH || e->cfg.precision == OAZ_FP32_SPLIT16) &&
                             tree_seg_kernels();
@@ -1004,6 +1052,33 @@ static int search_lat(oaz_engine* e, const Search& S) {
     return 0;
 }
 
+// k_search_par: the whole leaf-parallel search in one launch.
+static int search_par(oaz_engine* e, const Search& S) {
+    e->times.parts = 1;
+    const ParBufs b{e->par_path, e->par_depth, e->par_leaf, e->par_state, e->par_policy, e->par_value, e->par_stats};
+    if (int rc = timed(e, K_BACKUP_SELECT, S.t.G, [&] {
+            return launch_search_par(S.t, S.roots, S.prm, (int)S.sims, (int)e->cfg.leaf_batch, S.net, b, S.deadline,
+                                     S.sims_run, e->stream);
+        }))
+        return rc;
+    e->par_G = S.t.G;
+    e->last.sims = S.sims;  // (with a budget: replaced by the roots' largest count when it is asked for)
+    return 0;
+}
+
+// An engine with leaf_batch > 0 runs k_search_par or nothing: the searches it cannot take fail here, before
+// anything is launched.
+static int par_search_check(const oaz_engine* e, uint32_t G, const char* who) {
+    if (e->cfg.leaf_batch == 0) return 0;
+    if (e->cfg.train_noise)
+        return oaz_set_err(OAZ_ERR_STATE, "%s: leaf_batch=%d does not run with root noise (train_noise = 1)", who,
+                           e->cfg.leaf_batch);
+    if (G > (uint32_t)e->cus)
+        return oaz_set_err(OAZ_ERR_STATE, "%s: leaf_batch=%d searches at most %d roots (one workgroup per CU), got %u", who,
+                           e->cfg.leaf_batch, e->cus, G);
+    return 0;
+}
+
 // k_search_grp: chunk c's simulations in one launch (the one part: every game, on the engine stream), each
 // workgroup walking, evaluating and backing up its 16 games without a grid-wide step.
 static int grp_chunk(oaz_engine* e, const Search& S, const NoiseRing& ring, uint32_t c) {
@@ -1113,7 +1188,7 @@ static int run_sims(oaz_engine* e, const TreeView& t, const oaz_state* roots, co
     }
     e->last = LastSearch{t.G};
     int rc = path == PATH_STEPS ? 0 : arm_device_budget(e, t.G);
-    if (!rc) rc = path == PATH_LAT ? search_lat(e, S) : run_chunks(e, S, path == PATH_GRP);
+    if (!rc) rc = path == PATH_PAR ? search_par(e, S) : path == PATH_LAT ? search_lat(e, S) : run_chunks(e, S, path == PATH_GRP);
     if (rc) {
         const std::string msg = g_err;
         for (int h = 1; h < kMaxParts; ++h)
@@ -1151,6 +1226,7 @@ static void fill_search_stats(const uint64_t* s, oaz_search_stats* o) {
 // search ends what tree reuse may go on from (`searched` = 0); oaz_search and oaz_search_resume, the two searches
 // oaz_search_advance follows, set it again (searched_trees), the arena's resident search does not.
 static int search_core(oaz_engine* e, const oaz_state* roots, int G, bool keep_trees = false) {
+    if (int rc = par_search_check(e, (uint32_t)G, "search")) return rc;
     e->ply_trees = false;
     e->searched = 0;
     if (int rc = begin_budget(e)) return rc;
@@ -1272,8 +1348,16 @@ extern "C" int oaz_tree_dump(oaz_engine* e, int game, oaz_node* out, int cap, in
 }
 
 // ---- self-play ----------------------------------------------------------------------------------
+// Self-play is not part of the leaf-parallel search: such an engine refuses it (no other algorithm runs instead).
+static int par_no_selfplay(const oaz_engine* e, const char* who) {
+    if (e->cfg.leaf_batch == 0) return 0;
+    return oaz_set_err(OAZ_ERR_STATE, "%s: the engine was made with leaf_batch=%d, which searches only (no self-play)",
+                       who, e->cfg.leaf_batch);
+}
+
 extern "C" int oaz_selfplay_reset(oaz_engine* e) {
     if (!e) return oaz_set_err(OAZ_ERR_ARG, "selfplay_reset: null");
+    if (int rc = par_no_selfplay(e, "selfplay_reset")) return rc;
     OAZ_ON_DEVICE(e->device);
     const TreeView t = tree_view(e, e->G);
     HIP_TRY(hipMemsetAsync(e->stats, 0, (size_t)e->G * GS_COUNT * sizeof(uint64_t), e->stream));
@@ -1291,6 +1375,7 @@ extern "C" int oaz_selfplay_reset(oaz_engine* e) {
 
 extern "C" int oaz_selfplay_step(oaz_engine* e, int moves) {
     if (!e || moves < 0) return oaz_set_err(OAZ_ERR_ARG, "selfplay_step: bad arguments");
+    if (int rc = par_no_selfplay(e, "selfplay_step")) return rc;
     if (!e->selfplay_ready)
         if (int rc = oaz_selfplay_reset(e)) return rc;
     OAZ_ON_DEVICE(e->device);
@@ -1427,6 +1512,7 @@ static uint64_t rank_share(const oaz_engine* e, uint64_t quota) {
 extern "C" int oaz_selfplay_run(oaz_engine* e, int n_games, oaz_sample* out, size_t cap, size_t* n_out,
                                 oaz_selfplay_stats* stats) {
     if (!e || n_games < 0) return oaz_set_err(OAZ_ERR_ARG, "selfplay_run: bad arguments");
+    if (int rc = par_no_selfplay(e, "selfplay_run")) return rc;
     e->quota = (uint64_t)n_games;  // slots stop dealing at global game index >= n_games
     const uint64_t mine = rank_share(e, e->quota);  // this rank's share of the n_games (global) games
     int rc = oaz_selfplay_reset(e);

@@ -1,8 +1,10 @@
 // oaz_gpu.hip — one translation unit for the rules / search kernels (oaz_kernels.hip), the network
 // kernels (oaz_nn.hip), the one-launch small-batch search (oaz_search_lat.hip), which inlines the
-// device bodies of both (tree walk + network in one workgroup), and tree reuse (oaz_tree_reuse.hip), which
-// uses the tree kernels' device helpers.
+// device bodies of both (tree walk + network in one workgroup), the leaf-parallel search (oaz_search_par.hip),
+// which does the same with a tile of leaves per root, and tree reuse (oaz_tree_reuse.hip), which uses the tree
+// kernels' device helpers.
 #include "oaz_kernels.hip"
 #include "oaz_nn.hip"
 #include "oaz_search_lat.hip"
+#include "oaz_search_par.hip"
 #include "oaz_tree_reuse.hip"

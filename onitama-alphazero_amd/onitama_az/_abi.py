@@ -63,7 +63,14 @@ class oaz_sample(C.Structure):
     _fields_ = [("state", oaz_state), ("pi", C.c_float * 50), ("z", C.c_float)]
 
 
+class _oaz_config_pad0(C.Union):
+    """Bytes 70-71 of oaz_config: `pad0` is the two bytes a caller of the header before leaf_batch zeroes as
+    padding; the header now names the first of them leaf_batch (0 = off) and keeps pad0[1] for the second."""
+    _fields_ = [("leaf_batch", C.c_uint8), ("pad0", C.c_uint8 * 2)]
+
+
 class oaz_config(C.Structure):
+    _anonymous_ = ("_pad0",)
     _fields_ = [
         ("blocks", C.c_int32),
         ("channels", C.c_int32),
@@ -80,7 +87,7 @@ class oaz_config(C.Structure):
         ("fixed_deck", C.c_int32),
         ("deck", C.c_uint8 * 5),
         ("temperature_plies", C.c_uint8),
-        ("pad0", C.c_uint8 * 2),
+        ("_pad0", _oaz_config_pad0),  # leaf_batch (offset 70) and the header's pad0[1] (71); see above
         ("seed", C.c_uint64),
         ("rank", C.c_int32),
         ("world", C.c_int32),
@@ -288,6 +295,7 @@ assert C.sizeof(oaz_sample) == 228
 assert C.sizeof(oaz_config) == 120 and oaz_config.search_time_ns.offset == 104
 assert oaz_config.reuse_visits.offset == 116 and C.sizeof(oaz_reuse_stats) == 32
 assert oaz_config.temperature_plies.offset == 69 and oaz_config.seed.offset == 72
+assert oaz_config.leaf_batch.offset == 70
 assert C.sizeof(oaz_arena_agent) == 88 and C.sizeof(oaz_arena_config) == 40 and C.sizeof(oaz_fight_stats) == 96
 assert C.sizeof(oaz_arena_slots_stats) == 40
 
@@ -355,6 +363,7 @@ _PROTOS = {
     "oaz_search": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _VOIDP, _VOIDP, _VOIDP, _P(oaz_search_stats)]),
     "oaz_tree_dump": (C.c_int, [_VOIDP, C.c_int, _VOIDP, C.c_int, _P(C.c_int)]),
     "oaz_search_advance": (C.c_int, [_VOIDP, _VOIDP, C.c_int, _VOIDP]),
+    "oaz_search_leaf_batch_stats": (C.c_int, [_VOIDP, _P(C.c_uint64 * 3)]),
     "oaz_search_resume": (C.c_int, [_VOIDP, C.c_int, _VOIDP, _VOIDP, _VOIDP, _P(oaz_search_stats), _VOIDP]),
     "oaz_reuse_stats_get": (C.c_int, [_VOIDP, _P(oaz_reuse_stats)]),
     "oaz_tree_rebase_host": (C.c_int, [_VOIDP, C.c_int, C.c_int, _VOIDP, C.c_int, _P(C.c_int)]),

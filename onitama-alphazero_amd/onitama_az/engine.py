@@ -88,6 +88,14 @@ class Engine:
         _abi.check(self._lib.oaz_search_playouts(self._h, _abi.ptr(out), int(games)))
         return out
 
+    def leaf_batch_stats(self) -> Tuple[int, int, int]:
+        """Engine(leaf_batch=L), L = 1 .. 16 (the leaf-parallel search: up to L leaves of a root's tree per network
+        pass, virtual loss): (rounds, playouts, discarded walks) of the last search, summed over its roots; all 0
+        with leaf_batch = 0."""
+        out = (C.c_uint64 * 3)()
+        _abi.check(self._lib.oaz_search_leaf_batch_stats(self._h, C.byref(out)))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def sync(self) -> None:
         _abi.check(self._lib.oaz_sync(self._h))
 

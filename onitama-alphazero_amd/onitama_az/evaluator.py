@@ -380,9 +380,10 @@ class Evaluator:  # evaluator.rs:139-193
 
         def release(ms):  # a fight's engines (the reference drops each fight's VarStores)
             for m in ms:
-                eng = m.__dict__.get("_search", {}).get("engine")
-                if eng is not None:
-                    eng.close()
+                for name, shared in m.__dict__.items():  # "_search", and "_search_lb<L>" of leaf-batching agents
+                    eng = shared.get("engine") if name.startswith("_search") and isinstance(shared, dict) else None
+                    if eng is not None:
+                        eng.close()
 
         try:
             if concurrent:

@@ -31,6 +31,11 @@ class AlphaZeroMctsConfig:  # alphazero_mcts/mod.rs:26-43
     # simulation step that passes the budget. False runs exactly max_playouts playouts per search (the
     # parity and throughput mode: bench.py's arena line, the engine-level self-play)
     enforce_search_time: bool = True
+    # Leaf-parallel search (oaz_config.leaf_batch; not in the reference): 0 = off, the sequential search. L = 1 .. 16:
+    # a search of at most CU-count positions collects up to L leaves of a position's tree per network pass (virtual
+    # loss) and evaluates them as one tile; L = 1 is the sequential search, larger L trades a different (still
+    # exactly specified) tree for fewer, fuller network passes. Not with train = True (root noise)
+    leaf_batch: int = 0
 
 
 def reward(move_result: MoveResult, reward_color: PlayerColor) -> float:  # mod.rs:45-53
@@ -104,9 +109,11 @@ def _search_engine(cache: dict, config: AlphaZeroMctsConfig, model: ConvResNet, 
     """The model's search engine, shared by every agent that uses the model (the reference shares
     one Arc<Mutex<ConvResNet>> between agent clones, mod.rs:84,124): it is rebuilt only when the
     batch or the simulation budget outgrows it; each agent's AlphaZeroMctsConfig is applied with
-    oaz_set_search_params before its search."""
-    shared = model.__dict__.setdefault("_search", {})
-    key = (model.config.resnet_block_amnt, model.options.device, model.options.precision, id(model.weights))
+    oaz_set_search_params before its search. leaf_batch is fixed at an engine's creation, so agents with
+    different leaf_batch on one model each get an engine of their own (the model's "_search_lb<L>" entry)."""
+    lb = int(config.leaf_batch)
+    shared = model.__dict__.setdefault("_search" if lb == 0 else "_search_lb%d" % lb, {})
+    key = (model.config.resnet_block_amnt, model.options.device, model.options.precision, id(model.weights), lb)
     eng = shared.get("engine")
     if eng is None or shared.get("key") != key or shared["games"] < games or shared["sims"] < config.max_playouts:
         if eng is not None:
@@ -114,7 +121,7 @@ def _search_engine(cache: dict, config: AlphaZeroMctsConfig, model: ConvResNet, 
         g, n = max(games, shared.get("games", 0)), max(config.max_playouts, shared.get("sims", 0))
         eng = Engine(device=model.options.device, games=g, sims=n, c_puct=config.exploration_c,
                      train_noise=int(config.train), blocks=model.config.resnet_block_amnt, evaluator=_abi.EVAL_NN,
-                     precision=model.options.precision)
+                     precision=model.options.precision, leaf_batch=lb)
         eng.load_weights(model.weights)
         shared.update(engine=eng, key=key, games=g, sims=n)
     eng.set_search_params(config.max_playouts, config.exploration_c, config.train)

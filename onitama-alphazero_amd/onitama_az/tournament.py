@@ -58,9 +58,11 @@ class PairingResult:
     decks: List[List[int]] = field(default_factory=list)  # the pairing's deals: the tournament's
 
 
-def default_agents(model, seed: int = 20260101, device: int = 0) -> dict:
+def default_agents(model, seed: int = 20260101, device: int = 0, leaf_batch: int = 0) -> dict:
     """tournament.rs:107-134: AlphaBeta{8, 1 s}, Mcts{1 s, min visits 0, c 1.0, 5 000 playouts},
-    AlphaZeroMcts{1 s, c 1.0, 5 000 playouts, no noise} on `model` (a ConvResNet), Random."""
+    AlphaZeroMcts{1 s, c 1.0, 5 000 playouts, no noise} on `model` (a ConvResNet), Random. leaf_batch: the
+    AlphaZero agent's AlphaZeroMctsConfig.leaf_batch (0: the reference's sequential search; L > 0 searches at most
+    CU-count games per ply, i.e. game_amnt <= the device's CU count)."""
     from .alpha_beta import AlphaBeta
     from .arena import NativeRandomAgent
     from .mcts import AlphaZeroMctsConfig
@@ -69,7 +71,7 @@ def default_agents(model, seed: int = 20260101, device: int = 0) -> dict:
         "alphabeta": AlphaBeta(max_depth=8, search_time=1.0, device=device, enforce_search_time=True),
         "mcts": Mcts(search_time=1.0, min_node_visits=0, exploration_c=1.0, max_playouts=5000, seed=seed, device=device),
         "alphazero": AlphaZeroAgent(AlphaZeroMctsConfig(search_time=1.0, exploration_c=1.0, max_playouts=5000,
-                                                        train=False), model),
+                                                        train=False, leaf_batch=leaf_batch), model),
         "random": NativeRandomAgent(seed),
     }
 
