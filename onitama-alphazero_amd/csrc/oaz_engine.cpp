@@ -1055,10 +1055,10 @@ static int search_lat(oaz_engine* e, const Search& S) {
 // k_search_par: the whole leaf-parallel search in one launch.
 static int search_par(oaz_engine* e, const Search& S) {
     e->times.parts = 1;
-    const ParBufs b{e->par_path, e->par_depth, e->par_leaf, e->par_state, e->par_policy, e->par_value, e->par_stats};
+    const ParBufs b{e->par_path,   e->par_depth, e->par_leaf,  e->par_state,
+                    e->par_policy, e->par_value, e->par_stats, (uint32_t)e->cfg.leaf_batch};
     if (int rc = timed(e, K_BACKUP_SELECT, S.t.G, [&] {
-            return launch_search_par(S.t, S.roots, S.prm, (int)S.sims, (int)e->cfg.leaf_batch, S.net, b, S.deadline,
-                                     S.sims_run, e->stream);
+            return launch_search_par(S.t, S.roots, S.prm, (int)S.sims, S.net, b, S.deadline, S.sims_run, e->stream);
         }))
         return rc;
     e->par_G = S.t.G;

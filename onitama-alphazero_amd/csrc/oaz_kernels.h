@@ -175,21 +175,24 @@ __attribute__((weak)) hipError_t launch_selfplay_move_temp(const TreeView& t, co
                                                            uint64_t* counters, hipStream_t st);
 // Leaf-parallel search (oaz_config.leaf_batch = L > 0; oaz_search_par.hip, DESIGN.md "Leaf-parallel search"): all
 // `sims` playouts of every root in one launch, one workgroup per root, up to L leaves of the root's tree per
-// network pass (virtual loss in oaz_node.pad). The per-root records of a round, allocated by such an engine only:
+// network pass (virtual loss in oaz_node.pad). The per-root records of a round, allocated by such an engine only
+// (the engine fills this, the kernel takes it as it is):
 struct ParBufs {
     uint32_t* path;         // [G][L][pathcap]
     uint32_t* depth;        // [G][L]
     uint32_t* leaf;         // [G][L]
-    oaz_state* leaf_state;  // [G][16] the round's leaf positions (a whole 16-position tile per root)
+    oaz_state* leaf_state;  // [G][16] the round's leaf positions (a whole 16-position tile per root: rows L .. 15
+                            // are never used)
     float* policy;          // [G][16][50] and their evaluations
     float* value;           // [G][16]
     uint64_t* lb_stats;     // [G][3] rounds, playouts, discarded walks of the search (oaz_search_leaf_batch_stats)
+    uint32_t L;             // oaz_config.leaf_batch, 1 .. 16
 };
 // w = the fp16x3 network, or null for the HASH test evaluator; no root noise; deadline / sims_run as
 // launch_search_lat's, read before every round after the first (sims_run[g] = root g's playouts). Weak for the
 // same reason as the two above: an engine with leaf_batch > 0 cannot be made without it.
 __attribute__((weak)) hipError_t launch_search_par(const TreeView& t, const oaz_state* roots, SearchParams p, int sims,
-                                                   int leaf_batch, const NNView* w, const ParBufs& b,
-                                                   const uint64_t* deadline, uint32_t* sims_run, hipStream_t st);
+                                                   const NNView* w, const ParBufs& b, const uint64_t* deadline,
+                                                   uint32_t* sims_run, hipStream_t st);
 
 }  // namespace oaz

@@ -287,20 +287,30 @@ __global__ void __launch_bounds__(kBlock) k_root_noise(const oaz_state* __restri
 }
 
 // ---- MCTS kernels -------------------------------------------------------------------------
-struct NodeRegs {  // one node held in registers (all 32 bytes)
+// One node held in registers. VL: with its in-flight count v (oaz_node.pad, the leaf-parallel search's virtual
+// loss); every other user neither loads nor holds it.
+template <bool VL>
+struct NodeRegsT {
     double W, P;
     uint32_t N, first, misc;  // misc = mv | nch<<16 | flags<<24
 };
+template <>
+struct NodeRegsT<true> : NodeRegsT<false> {
+    uint32_t v;
+};
+using NodeRegs = NodeRegsT<false>;
 
-__device__ __forceinline__ NodeRegs load_node(const oaz_node* p) {
+template <bool VL = false>
+__device__ __forceinline__ NodeRegsT<VL> load_node(const oaz_node* p) {
     const uint4* q = reinterpret_cast<const uint4*>(p);
     const uint4 a = q[0], b = q[1];
-    NodeRegs r;
+    NodeRegsT<VL> r;
     r.W = __builtin_bit_cast(double, ((uint64_t)a.y << 32) | a.x);
     r.P = __builtin_bit_cast(double, ((uint64_t)a.w << 32) | a.z);
     r.N = b.x;
     r.first = b.y;
     r.misc = b.z;
+    if constexpr (VL) r.v = b.w;
     return r;
 }
 __device__ __forceinline__ int node_nch(uint32_t misc) { return (misc >> 16) & 0xFF; }
@@ -640,6 +650,8 @@ __device__ __forceinline__ int root_fold(int K, int Kmax, const NodeRegs (&ch)[3
 // table (one dependent load per tree level) and the game's root position.
 struct NodesGlobal {
     __device__ __forceinline__ oaz_node* at(oaz_node* T, uint32_t i) const { return T + i; }
+    // child l of a node whose children start at `first` (a lane's own l folds into the base, outside the walk)
+    __device__ __forceinline__ oaz_node* child(oaz_node* T, uint32_t first, int l) const { return T + first + l; }
     __device__ __forceinline__ double sqrt_n(const TreeView& t, uint32_t n) const { return t.sqrt_tab[n]; }
     __device__ __forceinline__ const oaz_state* root(const oaz_state* roots, uint32_t g) const { return &roots[g]; }
     __device__ __forceinline__ void add(uint64_t* st, int f, uint64_t v) const { stat_add(&st[f], v); }
@@ -670,6 +682,7 @@ struct NodesCached {
     const oaz_state* rt;  // LDS: the workgroup's game's root position
     uint64_t* stl;        // LDS: the game's statistics, added to its global slots once at the end of the launch
     __device__ __forceinline__ oaz_node* at(oaz_node* T, uint32_t i) const { return i < n ? L + i : T + i; }
+    __device__ __forceinline__ oaz_node* child(oaz_node* T, uint32_t first, int l) const { return at(T, first + l); }
     __device__ __forceinline__ double sqrt_n(const TreeView& t, uint32_t k) const {
         return k < nsq ? sq[k] : t.sqrt_tab[k];
     }
@@ -980,6 +993,129 @@ __device__ __forceinline__ void select_seg_body(const TreeView& t, const oaz_sta
             if (ssum) na.add(st, GS_STUCK, ssum);
         }
     }
+}
+
+// The walk of ONE game on a whole wave (the one-launch searches' walkers: k_search_lat, k_search_par): lane l
+// holds child l (K <= 40 < 64), so a level evaluates each child's PUCT once instead of three children per lane
+// of a 16-lane segment. Same expressions and the same last-maximum rule as select_seg_body / k_select
+// (mcts_arena.rs:183-223): the arg-max runs within each 16-lane row by DPP and across the four rows on scalars,
+// the chosen child's fields are read from its lane with v_readlane. No root noise. t is the game's own view
+// (G = 1), Tr its nodes, pathr the walk's path record (lane 0 writes it), na.root(root, 0) its root position.
+// VL: on the effective statistics of the leaf-parallel search, n = N + v, w = W - (double)v, v the node's
+// in-flight count. DBG (diagnostic build): s_memtime cycles of the prologue (root position and node) into
+// GS_MOVES, and of each level's child loads + PUCT keys summed in dbg_cycles.
+// Leaves in w, uniform over the wave, the leaf the walk ended on; what is recorded of it is the caller's.
+template <bool VL>
+struct WideLeaf {
+    oaz_state s;         // the leaf position, to_move set
+    NodeRegsT<VL> nd;    // the leaf's N, first, misc (its terminal flag set if the walk's move won) and v
+    uint32_t node, depth;
+    bool stuck;          // the walk stopped on an expanded node without children
+    uint64_t dbg_cycles;
+};
+template <class NA, bool VL, int DBG>
+__device__ __forceinline__ void select_wide_body(WideLeaf<VL>& w, const TreeView& t, oaz_node* const& Tr,
+                                                 uint32_t* const& pathr, const oaz_state* root,
+                                                 const SearchParams& prm, const NA& na) {
+    uint64_t d0 = DBG ? __builtin_amdgcn_s_memtime() : 0, dl = 0;
+    oaz_node* const T = Tr;  // (by reference: k_search_lat's are fields of t, read after the DBG stamp)
+    uint32_t* const path = pathr;
+    const int l = (int)(threadIdx.x & 63);
+    oaz_state& s = w.s;  // (walked in place: a copy of the position at the end compiles to other code)
+    s = load_state(na.root(root, 0));
+    int color = s.to_move & 1;
+    NodeRegsT<VL> nd = load_node<VL>(na.at(T, 0));
+    uint32_t node = 0, depth = 0;
+    if (l == 0) path[0] = 0;
+    bool stuck = false;
+    if constexpr (DBG) {
+        asm volatile("" ::"v"(nd.misc), "v"(s.pawns[0]));
+        const uint64_t d1 = __builtin_amdgcn_s_memtime();
+        if (l == 0) na.add(nullptr, GS_MOVES, d1 - d0);
+    }
+    while ((node_flags(nd.misc) & 1) && !(node_flags(nd.misc) & 2)) {
+        const int K = node_nch(nd.misc);
+        if (K == 0) {  // reference would panic in select (Q6): stop here, treat as a leaf
+            stuck = true;
+            break;
+        }
+        const uint64_t da = DBG ? __builtin_amdgcn_s_memtime() : 0;
+        NodeRegsT<VL> ch;
+        ch.W = 0.0;
+        ch.P = 0.0;
+        ch.N = 0;
+        ch.first = 0;
+        ch.misc = 0;
+        if constexpr (VL) ch.v = 0;
+        if (l < K) ch = load_node<VL>(na.child(T, nd.first, l));
+        double sqn;
+        if constexpr (VL) sqn = na.sqrt_n(t, nd.N + nd.v);  // N_p + v_p <= sims
+        else sqn = na.sqrt_n(t, nd.N);
+        int64_t key = INT64_MIN;
+        if (l < K) {  // mcts_arena.rs:204-207, with VL on the effective statistics
+            double q, sq;
+            if constexpr (VL) {
+                const uint32_t n = ch.N + ch.v;
+                q = n ? (ch.W - (double)ch.v) / (double)n : 0.0;
+                sq = sqn / (double)(n + 1);
+            } else {
+                q = ch.N ? ch.W / (double)ch.N : 0.0;
+                sq = sqn / (double)(ch.N + 1);
+            }
+            const double u = q + prm.c_puct * ch.P * sq;
+            key = total_key(u);
+        }
+        if constexpr (DBG) {
+            asm volatile("" ::"v"(key));
+            dl += __builtin_amdgcn_s_memtime() - da;
+        }
+        int idx = l;
+        seg_amax_step<0xB1>(key, idx);  // within each row of 16 lanes (every lane ends with its row's best)
+        seg_amax_step<0x4E>(key, idx);
+        seg_amax_step<0x141>(key, idx);
+        seg_amax_step<0x140>(key, idx);
+        int best = __builtin_amdgcn_readlane(idx, 0);
+        int64_t bkey = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)key >> 32), 0) << 32) |
+                                 (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)key, 0));
+#pragma unroll
+        for (int r = 1; r < 4; ++r) {  // rows hold ascending children: a tie goes to the later row
+            const int64_t rk =
+                (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)key >> 32), 16 * r) << 32) |
+                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)key, 16 * r));
+            const int ri = __builtin_amdgcn_readlane(idx, 16 * r);
+            if (rk > bkey || (rk == bkey && ri > best)) {
+                bkey = rk;
+                best = ri;
+            }
+        }
+        NodeRegsT<VL> c;  // (the walk reads only N, first, misc and v of the node it descends to)
+        c.W = 0.0;
+        c.P = 0.0;
+        c.N = (uint32_t)__builtin_amdgcn_readlane((int)ch.N, best);
+        c.first = (uint32_t)__builtin_amdgcn_readlane((int)ch.first, best);
+        c.misc = (uint32_t)__builtin_amdgcn_readlane((int)ch.misc, best);
+        if constexpr (VL) c.v = (uint32_t)__builtin_amdgcn_readlane((int)ch.v, best);
+        const uint32_t cidx = nd.first + (uint32_t)best;
+        const int res = na.move(s, mv_from(c.misc), mv_to(c.misc), mv_piece(c.misc), mv_slot(c.misc), color);
+        color ^= 1;  // game_state.player_color.switch()
+        if (is_win(res)) {
+            c.misc |= 2u << 24;
+            if (l == 0) {
+                uint8_t* const fp = flags_ptr(na.at(T, cidx));  // (in this order k_search_par's code is its old one)
+                *fp = (uint8_t)(node_flags(c.misc));
+            }
+        }
+        ++depth;
+        if (l == 0 && depth < t.pathcap) path[depth] = cidx;
+        node = cidx;
+        nd = c;
+    }
+    s.to_move = (uint8_t)color;
+    w.node = node;
+    w.depth = depth;
+    w.stuck = stuck;
+    w.nd = nd;
+    w.dbg_cycles = dl;
 }
 
 // register budget: 64 VGPRs = 8 waves/SIMD, no spill (the fold operands 40 KB: four workgroups per CU)

@@ -1586,6 +1586,42 @@ __device__ __noinline__ void nn_h3_fallback(const oaz_state* __restrict__ states
                                             float* lds) {
     nn_x6_body<X, GRP>(states, sp, xblob, blocks, policy, value, lds);
 }
+// The recompute of sp's positions and its count, by every thread of a workgroup that is past a barrier (the
+// fallback uses the whole LDS).
+template <class C>
+__device__ __forceinline__ void nn_h3_recompute(const oaz_state* states, const TileSpan sp, const float* xblob,
+                                                int blocks, float* policy, float* value, float* lds,
+                                                unsigned long long* fallback) {
+    using X = typename H3Fallback<C>::X;
+    if ((threadIdx.x >> 8) == 0)
+        nn_h3_fallback<X, X::GRP0>(states, sp, xblob, blocks, policy, value, lds);
+    else
+        nn_h3_fallback<X, X::GRP1>(states, sp, xblob, blocks, policy, value, lds);
+    if (threadIdx.x == 0) atomicAdd(fallback, 1ull);
+}
+
+// The evaluation of one 16-position tile by a workgroup of C::WAVES waves (k_nn_h3, and the one-launch searches
+// that evaluate a tile per round: k_search_grp, k_search_par): waves 0-3 take square group GRP0 (17 / 15
+// squares), 4-7 GRP1; a tile that left the fp16 range is recomputed and counted. opaque: as nn_h3_body's.
+// states: the caller's pointer to the positions, by reference, so that each branch reads it where the body uses
+// it, as when this sequence stood in the kernels. Read once before the branch (k_search_grp's is a field of its
+// tree view) it is one more value live across the body, whose registers are full, and that kernel's spills move.
+template <class C, class States>
+__device__ __forceinline__ void nn_h3_tile(const States& states, const TileSpan sp, const float* blob, int blocks,
+                                           const float* xblob, unsigned long long* fallback, float* policy,
+                                           float* value, float* lds, int opaque = 0) {
+    bool ovf;
+    if ((threadIdx.x >> 8) == 0) {
+        __builtin_amdgcn_s_setprio(1);  // (priority to the smaller group measured 6 % slower)
+        ovf = nn_h3_body<C, C::GRP0>(states, sp, blob, blocks, policy, value, lds, opaque);
+    } else {
+        ovf = nn_h3_body<C, C::GRP1>(states, sp, blob, blocks, policy, value, lds, opaque);
+    }
+    if constexpr (H3Fallback<C>::kOn) {
+        // uniform over the workgroup; also the barrier before LDS reuse
+        if (__syncthreads_or(ovf)) nn_h3_recompute<C>(states, sp, xblob, blocks, policy, value, lds, fallback);
+    }
+}
 
 template <class C>
 __global__ void __launch_bounds__(64 * C::WAVES) k_nn_h3(const oaz_state* __restrict__ states, int B,
@@ -1597,24 +1633,7 @@ __global__ void __launch_bounds__(64 * C::WAVES) k_nn_h3(const oaz_state* __rest
     // DBG 5 (timing only): the workgroup's start / end on the constant 100 MHz clock and its CU
     const uint64_t rt0 = C::DBG == 5 ? __builtin_amdgcn_s_memrealtime() : 0;
     const TileSpan sp = tile_span(tm, B);
-    bool ovf;
-    const bool g0 = (threadIdx.x >> 8) == 0;  // waves 0-3: square group GRP0 (17 / 15 squares), 4-7: GRP1
-    if (g0) {
-        __builtin_amdgcn_s_setprio(1);  // (priority to the smaller group measured 6 % slower)
-        ovf = nn_h3_body<C, C::GRP0>(states, sp, blob, blocks, policy, value, lds);
-    } else {
-        ovf = nn_h3_body<C, C::GRP1>(states, sp, blob, blocks, policy, value, lds);
-    }
-    if constexpr (H3Fallback<C>::kOn) {
-        using X = typename H3Fallback<C>::X;
-        if (__syncthreads_or(ovf)) {  // uniform over the workgroup; also the barrier before LDS reuse
-            if (g0)
-                nn_h3_fallback<X, X::GRP0>(states, sp, xblob, blocks, policy, value, lds);
-            else
-                nn_h3_fallback<X, X::GRP1>(states, sp, xblob, blocks, policy, value, lds);
-            if (threadIdx.x == 0) atomicAdd(fallback, 1ull);
-        }
-    }
+    nn_h3_tile<C>(states, sp, blob, blocks, xblob, fallback, policy, value, lds);
     if constexpr (C::DBG == 5) {
         __syncthreads();  // every wave is done
         if (threadIdx.x == 0 && sp.b0 < sp.end) {
@@ -2023,15 +2042,8 @@ __global__ void __launch_bounds__(64 * C::WAVES) k_nn_h3s(const oaz_state* __res
     if (b >= end) return;  // uniform over the workgroup
     const bool ovf = nn_h3s_body<C>(states, b, blob, blocks, policy, value, lds);
     if constexpr (H3Fallback<C>::kOn) {
-        using X = typename H3Fallback<C>::X;
-        if (__syncthreads_or(ovf)) {  // recompute this position as k_nn_h3 would (its fallback body)
-            const TileSpan sp{b, b + 1, cap};
-            if ((threadIdx.x >> 8) == 0)
-                nn_h3_fallback<X, X::GRP0>(states, sp, xblob, blocks, policy, value, lds);
-            else
-                nn_h3_fallback<X, X::GRP1>(states, sp, xblob, blocks, policy, value, lds);
-            if (threadIdx.x == 0) atomicAdd(fallback, 1ull);
-        }
+        if (__syncthreads_or(ovf))  // recompute this position as k_nn_h3 would (its fallback body)
+            nn_h3_recompute<C>(states, TileSpan{b, b + 1, cap}, xblob, blocks, policy, value, lds, fallback);
     }
 }
 

@@ -11,10 +11,12 @@
 // runs while the compute waves already hold the first conv's weights, and nothing is launched per
 // simulation.
 //
-// Same arithmetic as the per-step launches, bit for bit: the tree work is the segmented kernels' own
-// bodies (select_seg_body, expand_backup_seg_body: one 16-lane segment of wave 4 holds the game, the
-// other segments idle), the network is k_nn_h3s's body (bit-identical to k_nn_h3) with its in-kernel
-// fp16-range recompute, or the HASH test evaluator. Used when the per-step loop would launch one NN
+// Same arithmetic as the per-step launches, bit for bit: the walk is select_wide_body (oaz_kernels.hip: one
+// game on the whole of wave 4, select_seg_body's expressions), the expand / back up the segmented kernels' own
+// body (expand_backup_seg_body: one 16-lane segment of wave 4 holds the game, the other segments idle), the
+// network is k_nn_h3s's body (bit-identical to k_nn_h3) with the in-kernel fp16-range recompute
+// (nn_h3_recompute, oaz_nn.hip), or the HASH test evaluator. k_search_grp evaluates its 16 games as one tile
+// (nn_h3_tile, oaz_nn.hip). Used when the per-step loop would launch one NN
 // workgroup per game anyway (games <= CUs), with the fp16x3 network or HASH, no root noise (the
 // Agent / arena config, train = false) and no leaf compaction (oaz_engine.cpp run_sims;
 // oaz_config.step_kernels = 1 turns it off).
@@ -31,6 +33,14 @@
 namespace oaz {
 
 constexpr int kLatThreads = 512;  // 8 waves: k_nn_h3s's geometry; wave 4 also walks the tree
+
+// The launchers' common argument checks: a budget needs its counts, the network (null: HASH) its fp16-range
+// recompute.
+static hipError_t search_args_check(const uint64_t* deadline, const uint32_t* sims_run, const NNView* w) {
+    if (deadline && !sims_run) return hipErrorInvalidValue;
+    if (w && (!w->fallback || !w->blob_x6 || w->precision != OAZ_FP32_SPLIT16)) return hipErrorInvalidValue;
+    return hipSuccess;
+}
 
 // LDS of k_search_lat beside the network's (h3s::kBytes): the walker's per-game records (leaf position,
 // leaf, depth, node count), the leaf's evaluation (the network's heads write it here), the game's statistics,
@@ -72,104 +82,23 @@ __device__ __noinline__ void lat_backup(const TreeView& t, const oaz_state* root
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
-// The walk of the workgroup's one game on the whole walker wave: lane l holds child l (K <= 40 < 64), so a
-// level evaluates each child's PUCT once instead of three children per lane of a 16-lane segment. Same
-// expressions and the same last-maximum rule as select_seg_body / k_select (mcts_arena.rs:183-223): the
-// arg-max runs within each 16-lane row by DPP and across the four rows on scalars, the chosen child's
-// fields are read from its lane with v_readlane. No root noise here (k_search_lat's condition).
-// DBG (diagnostic build): s_memtime cycles of the prologue (root position and node) into GS_MOVES and of each
-// level's child loads + PUCT keys into GS_FINISHED
+// The walk of the workgroup's one game on the whole walker wave: select_wide_body (oaz_kernels.hip) on the LDS
+// copies (NodesCached), then the leaf's records into LDS, where the network and the backup read them.
+// DBG (diagnostic build): select_wide_body's cycle stamps, its per-level sum into GS_FINISHED
 template <int DBG = 0>
 __device__ __noinline__ void lat_select_wide(const TreeView& t, const SearchParams& prm, const NodesCached& na) {
-    uint64_t d0 = DBG ? __builtin_amdgcn_s_memtime() : 0, dl = 0;
-    const int l = (int)(threadIdx.x & 63);
-    oaz_node* T = t.nodes;
-    uint32_t* path = t.path;
-    oaz_state s = load_state(na.rt);
-    int color = s.to_move & 1;
-    NodeRegs nd = load_node(na.at(T, 0));
-    uint32_t node = 0, depth = 0;
-    if (l == 0) path[0] = 0;
-    bool stuck = false;
-    if constexpr (DBG) {
-        asm volatile("" ::"v"(nd.misc), "v"(s.pawns[0]));
-        const uint64_t d1 = __builtin_amdgcn_s_memtime();
-        if (l == 0) na.add(nullptr, GS_MOVES, d1 - d0);
-    }
-    while ((node_flags(nd.misc) & 1) && !(node_flags(nd.misc) & 2)) {
-        const int K = node_nch(nd.misc);
-        if (K == 0) {  // reference would panic in select (Q6): stop here, treat as a leaf
-            stuck = true;
-            break;
-        }
-        const uint64_t da = DBG ? __builtin_amdgcn_s_memtime() : 0;
-        NodeRegs ch;
-        ch.W = 0.0;
-        ch.P = 0.0;
-        ch.N = 0;
-        ch.first = 0;
-        ch.misc = 0;
-        if (l < K) ch = load_node(na.at(T, nd.first + l));
-        const double sqn = na.sqrt_n(t, nd.N);
-        int64_t key = INT64_MIN;
-        if (l < K) {
-            const double q = ch.N ? ch.W / (double)ch.N : 0.0;
-            const double sq = sqn / (double)(ch.N + 1);
-            const double u = q + prm.c_puct * ch.P * sq;  // mcts_arena.rs:204-207
-            key = total_key(u);
-        }
-        if constexpr (DBG) {
-            asm volatile("" ::"v"(key));
-            dl += __builtin_amdgcn_s_memtime() - da;
-        }
-        int idx = l;
-        seg_amax_step<0xB1>(key, idx);   // within each row of 16 lanes (every lane ends with its row's best)
-        seg_amax_step<0x4E>(key, idx);
-        seg_amax_step<0x141>(key, idx);
-        seg_amax_step<0x140>(key, idx);
-        int best = __builtin_amdgcn_readlane(idx, 0);
-        int64_t bkey = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)key >> 32), 0) << 32) |
-                                 (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)key, 0));
-#pragma unroll
-        for (int r = 1; r < 4; ++r) {  // rows hold ascending children: a tie goes to the later row
-            const int64_t rk =
-                (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)key >> 32), 16 * r) << 32) |
-                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)key, 16 * r));
-            const int ri = __builtin_amdgcn_readlane(idx, 16 * r);
-            if (rk > bkey || (rk == bkey && ri > best)) {
-                bkey = rk;
-                best = ri;
-            }
-        }
-        NodeRegs c;  // (the walk reads only N, first and misc of the node it descends to)
-        c.W = 0.0;
-        c.P = 0.0;
-        c.N = (uint32_t)__builtin_amdgcn_readlane((int)ch.N, best);
-        c.first = (uint32_t)__builtin_amdgcn_readlane((int)ch.first, best);
-        c.misc = (uint32_t)__builtin_amdgcn_readlane((int)ch.misc, best);
-        const uint32_t cidx = nd.first + (uint32_t)best;
-        const int res = make_move_regs(s, mv_from(c.misc), mv_to(c.misc), mv_piece(c.misc), mv_slot(c.misc), color);
-        color ^= 1;  // game_state.player_color.switch()
-        if (is_win(res)) {
-            c.misc |= 2u << 24;
-            if (l == 0) *flags_ptr(na.at(T, cidx)) = (uint8_t)(node_flags(c.misc));
-        }
-        ++depth;
-        if (l == 0 && depth < t.pathcap) path[depth] = cidx;
-        node = cidx;
-        nd = c;
-    }
-    s.to_move = (uint8_t)color;
-    if (l == 0) {
-        const bool need = leaf_needs_eval(nd.misc, s);
-        store_state(t.leaf_state, s);
-        *t.leaf = node;
-        *t.depth = depth;
+    WideLeaf<false> w;
+    select_wide_body<NodesCached, false, DBG>(w, t, t.nodes, t.path, nullptr, prm, na);
+    if ((threadIdx.x & 63) == 0) {
+        const bool need = leaf_needs_eval(w.nd.misc, w.s);
+        store_state(t.leaf_state, w.s);
+        *t.leaf = w.node;
+        *t.depth = w.depth;
         na.add(nullptr, GS_SIMS, 1);
-        na.add(nullptr, GS_DEPTH, depth);
+        na.add(nullptr, GS_DEPTH, w.depth);
         na.add(nullptr, GS_EVALS, need);
-        if (stuck) na.add(nullptr, GS_STUCK, 1);
-        if constexpr (DBG) na.add(nullptr, GS_FINISHED, dl);
+        if (w.stuck) na.add(nullptr, GS_STUCK, 1);
+        if constexpr (DBG) na.add(nullptr, GS_FINISHED, w.dbg_cycles);
     }
 }
 
@@ -341,13 +270,8 @@ __global__ void __launch_bounds__(kLatThreads) k_search_lat(TreeView t, const oa
                 flush_stats();
                 lat_sync_tree(tl, tg, na, path_lds, true);
                 __syncthreads();
-                using X = typename H3Fallback<C>::X;
                 const TileSpan span{(int)g, (int)g + 1, (int)t.G};
-                if ((threadIdx.x >> 8) == 0)
-                    nn_h3_fallback<X, X::GRP0>(t.leaf_state, span, xblob, blocks, policy, value, lds);
-                else
-                    nn_h3_fallback<X, X::GRP1>(t.leaf_state, span, xblob, blocks, policy, value, lds);
-                if (threadIdx.x == 0) atomicAdd(fallback, 1ull);
+                nn_h3_recompute<C>(t.leaf_state, span, xblob, blocks, policy, value, lds, fallback);
                 __syncthreads();
                 lat_sync_tree(tl, tg, na, path_lds, false);
                 fill_resident();
@@ -466,23 +390,7 @@ __global__ void __launch_bounds__(kLatThreads) k_search_grp(TreeView t, const oa
         } else {
             int opaque;  // 0, opaque to the compiler: no lane offset of the body is hoisted out of this loop
             asm volatile("v_mov_b32 %0, 0" : "=v"(opaque));
-            bool ovf;
-            if ((tid >> 8) == 0) {
-                __builtin_amdgcn_s_setprio(1);
-                ovf = nn_h3_body<C, C::GRP0>(t.leaf_state, span, blob, blocks, policy, value, lds, opaque);
-            } else {
-                ovf = nn_h3_body<C, C::GRP1>(t.leaf_state, span, blob, blocks, policy, value, lds, opaque);
-            }
-            if constexpr (H3Fallback<C>::kOn) {
-                using X = typename H3Fallback<C>::X;
-                if (__syncthreads_or(ovf)) {
-                    if ((tid >> 8) == 0)
-                        nn_h3_fallback<X, X::GRP0>(t.leaf_state, span, xblob, blocks, policy, value, lds);
-                    else
-                        nn_h3_fallback<X, X::GRP1>(t.leaf_state, span, xblob, blocks, policy, value, lds);
-                    if (tid == 0) atomicAdd(fallback, 1ull);
-                }
-            }
+            nn_h3_tile<C>(t.leaf_state, span, blob, blocks, xblob, fallback, policy, value, lds, opaque);
         }
         __syncthreads();  // policy / value rows written; the LDS is the tree's again
     }
@@ -503,49 +411,38 @@ __global__ void __launch_bounds__(kLatThreads) k_search_grp(TreeView t, const oa
 hipError_t launch_search_grp(const TreeView& t, const oaz_state* roots, const uint8_t* active, SearchParams p, int s0,
                              int s1, const noise_t* noise, const NNView* w, float* policy, float* value,
                              const uint64_t* deadline, uint32_t* sims_run, hipStream_t st) {
-    if (deadline && !sims_run) return hipErrorInvalidValue;
+    if (hipError_t bad = search_args_check(deadline, sims_run, w)) return bad;
     if (t.G == 0 || s1 <= s0) return hipSuccess;
-    if (w && (!w->fallback || !w->blob_x6 || w->precision != OAZ_FP32_SPLIT16)) return hipErrorInvalidValue;
     const unsigned grid = (t.G + nn::kSB - 1) / nn::kSB;
-#if OAZ_AB
+#if OAZ_AB  // the diagnostic instance, by environment variable
     static const int dbg = getenv("OAZ_GRP_DBG") ? atoi(getenv("OAZ_GRP_DBG")) : 0;
-    if (dbg == 1) {
-        hipLaunchKernelGGL((k_search_grp<H3Cfg<0>, 1>), dim3(grid), dim3(kLatThreads), 0, st, t, roots, active, p, s0, s1,
-                           noise, w ? 0 : 1, w ? w->blob : nullptr, w ? w->blocks : 0, w ? w->blob_x6 : nullptr,
-                           w ? w->fallback : nullptr, policy, value, deadline, sims_run);
-        return hipGetLastError();
-    }
+    const auto k = dbg == 1 ? k_search_grp<H3Cfg<0>, 1> : k_search_grp<H3Cfg<0>>;
+#else
+    const auto k = k_search_grp<H3Cfg<0>>;
 #endif
-    hipLaunchKernelGGL(k_search_grp<H3Cfg<0>>, dim3(grid), dim3(kLatThreads), 0, st, t, roots, active, p, s0, s1, noise,
-                       w ? 0 : 1, w ? w->blob : nullptr, w ? w->blocks : 0, w ? w->blob_x6 : nullptr,
-                       w ? w->fallback : nullptr, policy, value, deadline, sims_run);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kLatThreads), 0, st, t, roots, active, p, s0, s1, noise, w ? 0 : 1,
+                       w ? w->blob : nullptr, w ? w->blocks : 0, w ? w->blob_x6 : nullptr, w ? w->fallback : nullptr,
+                       policy, value, deadline, sims_run);
     return hipGetLastError();
 }
 
 hipError_t launch_search_lat(const TreeView& t, const oaz_state* roots, const uint8_t* active, SearchParams p,
                              int sims, const NNView* w, float* policy, float* value, const uint64_t* deadline,
                              uint32_t* sims_run, hipStream_t st) {
-    if (deadline && !sims_run) return hipErrorInvalidValue;
+    if (hipError_t bad = search_args_check(deadline, sims_run, w)) return bad;
     if (t.G == 0 || sims <= 0) return hipSuccess;
-    if (w && (!w->fallback || !w->blob_x6 || w->precision != OAZ_FP32_SPLIT16)) return hipErrorInvalidValue;
-#if OAZ_AB
+#if OAZ_AB  // the diagnostic instances, by environment variable
     static const int dbg = getenv("OAZ_LAT_DBG") ? atoi(getenv("OAZ_LAT_DBG")) : 0;
-    if (dbg == 2) {
-        hipLaunchKernelGGL(k_search_lat<2>, dim3(t.G), dim3(kLatThreads), 0, st, t, roots, active, p, sims, w ? 0 : 1,
-                           w ? w->blob : nullptr, w ? w->blocks : 0, w ? w->blob_x6 : nullptr,
-                           w ? w->fallback : nullptr, policy, value, deadline, sims_run);
-        return hipGetLastError();
-    }
-    if (dbg == 1) {
-        hipLaunchKernelGGL(k_search_lat<1>, dim3(t.G), dim3(kLatThreads), 0, st, t, roots, active, p, sims, w ? 0 : 1,
-                           w ? w->blob : nullptr, w ? w->blocks : 0, w ? w->blob_x6 : nullptr,
-                           w ? w->fallback : nullptr, policy, value, deadline, sims_run);
-        return hipGetLastError();
-    }
+    decltype(&k_search_lat<0>) k;
+    if (dbg == 2) k = k_search_lat<2>;
+    else if (dbg == 1) k = k_search_lat<1>;
+    else k = k_search_lat<0>;
+#else
+    const auto k = k_search_lat<0>;
 #endif
-    hipLaunchKernelGGL(k_search_lat<0>, dim3(t.G), dim3(kLatThreads), 0, st, t, roots, active, p, sims, w ? 0 : 1,
-                       w ? w->blob : nullptr, w ? w->blocks : 0, w ? w->blob_x6 : nullptr,
-                       w ? w->fallback : nullptr, policy, value, deadline, sims_run);
+    hipLaunchKernelGGL(k, dim3(t.G), dim3(kLatThreads), 0, st, t, roots, active, p, sims, w ? 0 : 1,
+                       w ? w->blob : nullptr, w ? w->blocks : 0, w ? w->blob_x6 : nullptr, w ? w->fallback : nullptr,
+                       policy, value, deadline, sims_run);
     return hipGetLastError();
 }
 

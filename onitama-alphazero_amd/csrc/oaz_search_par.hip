@@ -1,7 +1,7 @@
 // oaz_search_par.hip — leaf-parallel search with virtual loss (oaz_config.leaf_batch = L, 1 <= L <= 16;
 // DESIGN.md "Leaf-parallel search"): the whole search of a few roots in ONE launch, one workgroup per root as
-// k_search_lat, but a network pass evaluates up to L leaves of the SAME tree as one 16-position tile (k_nn_h3's
-// body, as k_search_grp runs it) where k_search_lat evaluates one.
+// k_search_lat, but a network pass evaluates up to L leaves of the SAME tree as one 16-position tile (nn_h3_tile,
+// oaz_nn.hip).
 //
 // The rule, in rounds until done == sims:
 //   collect  for j = 0 .. min(L, sims - done) - 1, in order: walk from the root as k_select does, on the
@@ -14,41 +14,26 @@
 //   back up  for j = 0 .. m - 1, in order: v -= 1 along path j, then the playout's expand / back up, unchanged
 //            (expand_backup_seg_body on leaf j's records); done += m.
 // With L = 1 this is the sequential search bit for bit (W - 0.0 == W). One walker wave (wave 0) runs the collect
-// and the back up sequentially in j; all eight waves evaluate the tile.
+// and the back up sequentially in j; all eight waves evaluate the tile. The walk is select_wide_body
+// (oaz_kernels.hip) on the effective statistics, the tile evaluation nn_h3_tile (oaz_nn.hip).
 //
 // The tree, the paths and the leaf records stay in global memory (L2): the tile body and its fp16-range
-// recompute use the kernel's whole LDS (H3Fallback::kLds, 157.7 KB of 160), which leaves no room for
-// k_search_lat's LDS copy of the top of the tree beside them.
+// recompute use the kernel's whole LDS (H3Fallback::kLds, 157.7 KB of 160), which leaves no room for an LDS
+// copy of the top of the tree beside them.
 //
 // Q7 search_time: thread 0 reads the device clock before every round after the first; a search stops only at a
 // round boundary, sims_run[g] = done.
 namespace oaz {
 
-struct ParNode {  // a node with its in-flight count
-    double W, P;
-    uint32_t N, first, misc, v;
-};
-__device__ __forceinline__ ParNode par_load_node(const oaz_node* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    ParNode r;
-    r.W = __builtin_bit_cast(double, ((uint64_t)a.y << 32) | a.x);
-    r.P = __builtin_bit_cast(double, ((uint64_t)a.w << 32) | a.z);
-    r.N = b.x;
-    r.first = b.y;
-    r.misc = b.z;
-    r.v = b.w;
-    return r;
-}
 __device__ __forceinline__ void par_fence() {  // the walker wave's own stores, visible to its other lanes
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// The collect phase of one round on the walker wave (all 64 lanes; lane l holds child l, K <= 40 < 64, as
-// lat_select_wide): up to `want` walks. t is the root's own view (G = 1; path / depth / leaf / leaf_state: leaf
-// 0's records, leaf j's follow at j * pathcap, j, j, j). Returns the leaves collected (uniform); *disc = 1 when a
-// discarded walk closed the round.
+// The collect phase of one round on the walker wave (all 64 lanes): up to `want` walks of select_wide_body on
+// the effective statistics. t is the root's own view (G = 1; path / depth / leaf / leaf_state: leaf 0's records,
+// leaf j's follow at j * pathcap, j, j, j). Returns the leaves collected (uniform); *disc = 1 when a discarded
+// walk closed the round.
 __device__ __noinline__ uint32_t par_collect(const TreeView& t, const oaz_state* root, const SearchParams& prm,
                                              uint32_t want, uint32_t* disc) {
     const int l = (int)(threadIdx.x & 63);
@@ -57,91 +42,25 @@ __device__ __noinline__ uint32_t par_collect(const TreeView& t, const oaz_state*
     *disc = 0;
     for (uint32_t j = 0; j < want; ++j) {
         uint32_t* path = t.path + (size_t)j * t.pathcap;
-        oaz_state s = load_state(root);
-        int color = s.to_move & 1;
-        ParNode nd = par_load_node(T);
-        uint32_t node = 0, depth = 0;
-        if (l == 0) path[0] = 0;
-        bool stuck = false;
-        while ((node_flags(nd.misc) & 1) && !(node_flags(nd.misc) & 2)) {
-            const int K = node_nch(nd.misc);
-            if (K == 0) {  // reference would panic in select (Q6): stop here, treat as a leaf
-                stuck = true;
-                break;
-            }
-            ParNode ch;
-            ch.W = 0.0;
-            ch.P = 0.0;
-            ch.N = 0;
-            ch.first = 0;
-            ch.misc = 0;
-            ch.v = 0;
-            if (l < K) ch = par_load_node(T + nd.first + l);
-            const double sqn = t.sqrt_tab[nd.N + nd.v];  // N_p + v_p <= sims
-            int64_t key = INT64_MIN;
-            if (l < K) {
-                const uint32_t n = ch.N + ch.v;
-                const double q = n ? (ch.W - (double)ch.v) / (double)n : 0.0;
-                const double sq = sqn / (double)(n + 1);
-                const double u = q + prm.c_puct * ch.P * sq;  // mcts_arena.rs:204-207 on the effective statistics
-                key = total_key(u);
-            }
-            int idx = l;
-            seg_amax_step<0xB1>(key, idx);  // within each row of 16 lanes (every lane ends with its row's best)
-            seg_amax_step<0x4E>(key, idx);
-            seg_amax_step<0x141>(key, idx);
-            seg_amax_step<0x140>(key, idx);
-            int best = __builtin_amdgcn_readlane(idx, 0);
-            int64_t bkey = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)key >> 32), 0) << 32) |
-                                     (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)key, 0));
-#pragma unroll
-            for (int r = 1; r < 4; ++r) {  // rows hold ascending children: a tie goes to the later row
-                const int64_t rk =
-                    (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)key >> 32), 16 * r) << 32) |
-                              (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)key, 16 * r));
-                const int ri = __builtin_amdgcn_readlane(idx, 16 * r);
-                if (rk > bkey || (rk == bkey && ri > best)) {
-                    bkey = rk;
-                    best = ri;
-                }
-            }
-            ParNode c;  // (the walk reads only N, first, misc and v of the node it descends to)
-            c.W = 0.0;
-            c.P = 0.0;
-            c.N = (uint32_t)__builtin_amdgcn_readlane((int)ch.N, best);
-            c.first = (uint32_t)__builtin_amdgcn_readlane((int)ch.first, best);
-            c.misc = (uint32_t)__builtin_amdgcn_readlane((int)ch.misc, best);
-            c.v = (uint32_t)__builtin_amdgcn_readlane((int)ch.v, best);
-            const uint32_t cidx = nd.first + (uint32_t)best;
-            const int res = make_move_regs(s, mv_from(c.misc), mv_to(c.misc), mv_piece(c.misc), mv_slot(c.misc), color);
-            color ^= 1;  // game_state.player_color.switch()
-            if (is_win(res)) {
-                c.misc |= 2u << 24;
-                if (l == 0) *flags_ptr(T + cidx) = (uint8_t)(node_flags(c.misc));
-            }
-            ++depth;
-            if (l == 0 && depth < t.pathcap) path[depth] = cidx;
-            node = cidx;
-            nd = c;
-        }
-        s.to_move = (uint8_t)color;
-        if (!(node_flags(nd.misc) & 3) && nd.v > 0) {  // this leaf is already in flight: the round closes here
+        WideLeaf<true> w;
+        select_wide_body<NodesGlobalRegs, true, 0>(w, t, T, path, root, prm, NodesGlobalRegs{});
+        if (!(node_flags(w.nd.misc) & 3) && w.nd.v > 0) {  // this leaf is already in flight: the round closes here
             *disc = 1;
             par_fence();  // (a terminal flag the walk set)
             break;
         }
         if (l == 0) {
-            const bool need = leaf_needs_eval(nd.misc, s);
-            store_state(t.leaf_state + j, s);
-            t.leaf[j] = node;
-            t.depth[j] = depth;
+            const bool need = leaf_needs_eval(w.nd.misc, w.s);
+            store_state(t.leaf_state + j, w.s);
+            t.leaf[j] = w.node;
+            t.depth[j] = w.depth;
             t.stats[GS_SIMS] += 1;  // one writer: this lane
-            t.stats[GS_DEPTH] += depth;
+            t.stats[GS_DEPTH] += w.depth;
             t.stats[GS_EVALS] += need;
-            if (stuck) t.stats[GS_STUCK] += 1;
+            if (w.stuck) t.stats[GS_STUCK] += 1;
         }
         par_fence();  // the path, written by lane 0
-        const uint32_t plen = depth < t.pathcap ? depth : t.pathcap - 1;
+        const uint32_t plen = w.depth < t.pathcap ? w.depth : t.pathcap - 1;
         for (uint32_t k = (uint32_t)l; k <= plen; k += 64) T[path[k]].pad += 1;  // (a path's nodes are distinct)
         par_fence();
         ++m;
@@ -173,21 +92,7 @@ __device__ __noinline__ void par_backup(const TreeView& t, const oaz_state* root
     }
 }
 
-// The per-root records of the leaf-parallel search (allocated with leaf_batch > 0 only): L paths, depths and
-// leaf ids per root, and 16 leaf positions and evaluation rows per root (a whole tile each: rows L .. 15 are
-// never used).
-struct ParView {
-    uint32_t* path;         // [G][L][pathcap]
-    uint32_t* depth;        // [G][L]
-    uint32_t* leaf;         // [G][L]
-    oaz_state* leaf_state;  // [G][16]
-    float* policy;          // [G][16][50]
-    float* value;           // [G][16]
-    uint64_t* lb_stats;     // [G][3] rounds, playouts, discarded walks of the search
-    uint32_t L;
-};
-
-__global__ void __launch_bounds__(kLatThreads) k_search_par(TreeView t, ParView pv, const oaz_state* __restrict__ roots,
+__global__ void __launch_bounds__(kLatThreads) k_search_par(TreeView t, ParBufs pv, const oaz_state* __restrict__ roots,
                                                             SearchParams prm, int sims, int hash_eval,
                                                             const float* __restrict__ blob, int blocks,
                                                             const float* __restrict__ xblob,
@@ -246,21 +151,7 @@ __global__ void __launch_bounds__(kLatThreads) k_search_par(TreeView t, ParView 
             const TileSpan span{b0, b0 + (int)m, (int)t.G * nn::kSB};
             int opaque;  // 0, opaque to the compiler: no lane offset of the body is hoisted out of this loop
             asm volatile("v_mov_b32 %0, 0" : "=v"(opaque));
-            bool ovf;
-            if ((tid >> 8) == 0) {
-                __builtin_amdgcn_s_setprio(1);
-                ovf = nn_h3_body<C, C::GRP0>(pv.leaf_state, span, blob, blocks, pv.policy, pv.value, lds, opaque);
-            } else {
-                ovf = nn_h3_body<C, C::GRP1>(pv.leaf_state, span, blob, blocks, pv.policy, pv.value, lds, opaque);
-            }
-            using X = typename H3Fallback<C>::X;
-            if (__syncthreads_or(ovf)) {
-                if ((tid >> 8) == 0)
-                    nn_h3_fallback<X, X::GRP0>(pv.leaf_state, span, xblob, blocks, pv.policy, pv.value, lds);
-                else
-                    nn_h3_fallback<X, X::GRP1>(pv.leaf_state, span, xblob, blocks, pv.policy, pv.value, lds);
-                if (tid == 0) atomicAdd(fallback, 1ull);
-            }
+            nn_h3_tile<C>(pv.leaf_state, span, blob, blocks, xblob, fallback, pv.policy, pv.value, lds, opaque);
         }
         __syncthreads();  // the evaluation rows written; the LDS is the tree's again
         if (walker) par_backup(tg, rg, pol, val, m, sp);
@@ -276,17 +167,14 @@ __global__ void __launch_bounds__(kLatThreads) k_search_par(TreeView t, ParView 
     }
 }
 
-hipError_t launch_search_par(const TreeView& t, const oaz_state* roots, SearchParams p, int sims, int leaf_batch,
-                             const NNView* w, const ParBufs& b, const uint64_t* deadline, uint32_t* sims_run,
-                             hipStream_t st) {
-    if (deadline && !sims_run) return hipErrorInvalidValue;
-    if (leaf_batch < 1 || leaf_batch > nn::kSB || !b.path || !b.depth || !b.leaf || !b.leaf_state || !b.policy ||
+hipError_t launch_search_par(const TreeView& t, const oaz_state* roots, SearchParams p, int sims, const NNView* w,
+                             const ParBufs& b, const uint64_t* deadline, uint32_t* sims_run, hipStream_t st) {
+    if (hipError_t bad = search_args_check(deadline, sims_run, w)) return bad;
+    if (b.L < 1 || b.L > (uint32_t)nn::kSB || !b.path || !b.depth || !b.leaf || !b.leaf_state || !b.policy ||
         !b.value || !b.lb_stats)
         return hipErrorInvalidValue;
     if (t.G == 0 || sims <= 0) return hipSuccess;
-    if (w && (!w->fallback || !w->blob_x6 || w->precision != OAZ_FP32_SPLIT16)) return hipErrorInvalidValue;
-    const ParView pv{b.path, b.depth, b.leaf, b.leaf_state, b.policy, b.value, b.lb_stats, (uint32_t)leaf_batch};
-    hipLaunchKernelGGL(k_search_par, dim3(t.G), dim3(kLatThreads), 0, st, t, pv, roots, p, sims, w ? 0 : 1,
+    hipLaunchKernelGGL(k_search_par, dim3(t.G), dim3(kLatThreads), 0, st, t, b, roots, p, sims, w ? 0 : 1,
                        w ? w->blob : nullptr, w ? w->blocks : 0, w ? w->blob_x6 : nullptr, w ? w->fallback : nullptr,
                        deadline, sims_run);
     return hipGetLastError();

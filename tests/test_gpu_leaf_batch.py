@@ -108,6 +108,45 @@ def test_network_tree_equals_the_rule(orc, trained3):
         assert r.stats.sims == 128 and e.leaf_batch_stats()[0] < 128  # rounds of more than one leaf
 
 
+@pytest.mark.parametrize("L", [1, 7])
+def test_network_recompute_tree_equals_the_rule(orc, trained3, L):
+    """Every evaluation leaves the fp16 range (the trained 3-block blob with the BN-folded first-layer bias at 1e5,
+    as test_one_launch_search_equals_step_launches' nn_overflow rows), so every round's tile takes the in-kernel
+    recompute: one-leaf rounds (L = 1) and an odd partial tile (L = 7), 3L + 5 playouts. The rule's evaluator is
+    one batch-1 forward per leaf of a second engine with the same weights; every round is counted as one
+    recomputed tile; and L = 1 is the leaf_batch = 0 search (k_search_lat's recompute) on the same weights."""
+    from onitama_az.weights import blob_from_named, named_from_blob
+    named = {k: v.copy() for k, v in named_from_blob(trained3.copy(), 3).items()}
+    named["bn1|bias"][:] = 1.0e5  # first-layer activations ~1e5 > 65504
+    bad = blob_from_named(named, 3)
+    roots = np.concatenate([start_root(orc, 0), midgame_roots(orc, 3)[1:2]])
+    sims, c = 3 * L + 5, math.sqrt(2.0)
+    kw = dict(games=2, sims=sims, c_puct=c, train_noise=0, evaluator=_abi.EVAL_NN, blocks=3,
+              precision=_abi.FP32_SPLIT16)
+
+    def dump(e, r):
+        return (r.moves.tobytes(), r.pi.tobytes(), [e.tree(g).tobytes() for g in range(2)],
+                (r.stats.sims, r.stats.expansions, r.stats.children, r.stats.terminal_leaves, r.stats.depth_sum,
+                 r.stats.stuck_leaves, r.stats.max_nodes, r.stats.nn_evals))
+
+    with Engine(leaf_batch=L, **kw) as e, Engine(games=4, sims=1, blocks=3, precision=_abi.FP32_SPLIT16) as ev:
+        e.load_weights(bad)
+        ev.load_weights(bad)
+
+        def evaluator(gs):
+            p, v = ev.nn_forward(lbr.state_np(gs, _abi.STATE_DTYPE))
+            return [float(x) for x in p.reshape(-1)], float(v[0])
+
+        r = _check_search(e, roots, sims, c, L, evaluator)
+        rounds = e.leaf_batch_stats()[0]
+        assert rounds > 0 and e.nn_fallbacks() == rounds  # a round is never empty and every tile overflows
+        par = dump(e, r)
+    if L == 1:
+        with Engine(leaf_batch=0, **kw) as e:
+            e.load_weights(bad)
+            assert dump(e, e.search(roots)) == par
+
+
 def test_search_time_budget_stops_at_a_round(orc):
     """A budget far below one search (1 us): each root stops at a round boundary with 1 <= playouts <= sims, its
     root visits are the reported playouts and no in-flight count is left. An ample budget (10 s) gives exactly
