@@ -414,13 +414,9 @@ extern "C" int oaz_alphabeta_evaluate(const oaz_state* s, const uint8_t* move_re
     return 0;
 }
 
-// Bitboards hold squares 0..24 only (the kernels index the attack table by square), cards are 0..15.
 static int check_roots(const oaz_state* roots, int G) {
     for (int g = 0; g < G; ++g)
-        if ((roots[g].to_move & ~1) || (roots[g].cards[0] | roots[g].cards[1] | roots[g].cards[2] | roots[g].cards[3] |
-                                        roots[g].cards[4]) > 15 ||
-            ((roots[g].kings[0] | roots[g].kings[1] | roots[g].pawns[0] | roots[g].pawns[1]) & 0x7Fu))
-            return oaz_set_err(OAZ_ERR_ARG, "alphabeta: root %d is not a valid state", g);
+        if (!oaz_root_ok(roots[g])) return oaz_set_err(OAZ_ERR_ARG, "alphabeta: root %d is not a valid state", g);
     return 0;
 }
 

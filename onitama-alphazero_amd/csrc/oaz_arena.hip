@@ -282,7 +282,7 @@ extern "C" int oaz_fight_stats_fold(const uint8_t* results, int n, double rating
 
 extern "C" int oaz_random_agent_move(uint64_t seed, uint64_t game, uint32_t ply, const oaz_state* s, oaz_move* out) {
     if (!s || !out) return oaz_set_err(OAZ_ERR_ARG, "random_agent_move: null argument");
-    if ((s->to_move & ~1) || (s->cards[0] | s->cards[1] | s->cards[2] | s->cards[3] | s->cards[4]) > 15)
+    if (!oaz_root_ok(*s, /*squares=*/false))  // (to_move and cards only: the squares are not looked at here)
         return oaz_set_err(OAZ_ERR_ARG, "random_agent_move: not a valid state");
     random_agent_move(kAttackHost, seed, game, ply, *s, *out);
     return 0;
@@ -292,12 +292,9 @@ static int check_arena_config(const oaz_arena_config* cfg) {
     if (!cfg) return oaz_set_err(OAZ_ERR_ARG, "arena: null config");
     if (cfg->game_amnt < 0) return oaz_set_err(OAZ_ERR_ARG, "arena: game_amnt %d", cfg->game_amnt);
     if (cfg->start) {  // (what the searches' own entry points ask of a root: squares 0..24, cards 0..15)
-        for (int k = 0; k < cfg->game_amnt; ++k) {
-            const oaz_state& s = cfg->start[k];
-            if ((s.to_move & ~1) || (s.cards[0] | s.cards[1] | s.cards[2] | s.cards[3] | s.cards[4]) > 15 ||
-                ((s.kings[0] | s.kings[1] | s.pawns[0] | s.pawns[1]) & 0x7Fu))
+        for (int k = 0; k < cfg->game_amnt; ++k)
+            if (!oaz_root_ok(cfg->start[k]))
                 return oaz_set_err(OAZ_ERR_ARG, "arena: start position %d is not a valid state", k);
-        }
     } else if (cfg->fixed_deck) {
         uint32_t seen = 0;
         for (int i = 0; i < 5; ++i) {

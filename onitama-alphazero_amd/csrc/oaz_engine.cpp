@@ -1022,8 +1022,7 @@ static int begin_budget(oaz_engine* e) {
     if (e->cfg.search_time_ns <= 0) return 0;
     e->t_search0 = now_ns();
     if (e->wall_khz <= 0) return 0;  // (no device clock: only the one-launch searches need it, arm_device_budget)
-    const double ticks = (double)e->cfg.search_time_ns * (double)e->wall_khz * 1e-6;
-    HIP_TRY(launch_deadline_start(e->deadline, ticks < 1.8e19 ? (uint64_t)ticks : (uint64_t)1.8e19, e->stream));
+    HIP_TRY(launch_deadline_start(e->deadline, oaz_budget_ticks(e->cfg.search_time_ns, e->wall_khz, 1.8e19), e->stream));
     return 0;
 }
 

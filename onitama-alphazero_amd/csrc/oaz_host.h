@@ -46,6 +46,20 @@ inline int oaz_check_device(const char* who, int device, int range_code = OAZ_ER
     return 0;
 }
 
+// What every entry point asks of a root: to_move 0 or 1, cards 0..15 and, with `squares`, bitboards that hold
+// squares 0..24 only (the searches' kernels index the attack table by square and by card).
+inline bool oaz_root_ok(const oaz_state& s, bool squares = true) {
+    return !(s.to_move & ~1) && (s.cards[0] | s.cards[1] | s.cards[2] | s.cards[3] | s.cards[4]) <= 15 &&
+           !(squares && ((s.kings[0] | s.kings[1] | s.pawns[0] | s.pawns[1]) & 0x7Fu));
+}
+
+// A search_time_ns budget in ticks of the device's constant-rate clock (hipDeviceAttributeWallClockRate, kHz),
+// at most `most`.
+inline uint64_t oaz_budget_ticks(int64_t search_time_ns, int wall_khz, double most) {
+    const double ticks = (double)search_time_ns * (double)wall_khz * 1e-6;
+    return ticks < most ? (uint64_t)ticks : (uint64_t)most;
+}
+
 // ---- owners of device resources ----------------------------------------------------------------------
 // Movable, not copyable; a default-made one holds nothing and its destructor does nothing. The destructors
 // run on the calling thread's current device, so whoever deletes a holder of owners is on the holder's

@@ -505,12 +505,27 @@ extern "C" void oaz_pure_mcts_config_default(oaz_pure_mcts_config* c) {  // ai/m
     c->game_id0 = 0;
 }
 
-extern "C" size_t oaz_pure_mcts_tree_capacity(const oaz_pure_mcts_config* c) {
-    if (!c || c->max_playouts < 0) return 0;
-    // every expanded node first collects min_node_visits + 1 playouts as a leaf, so a search
-    // expands at most playouts / (min_node_visits + 1) nodes, each with <= 40 children
-    const size_t exp = (size_t)c->max_playouts / (size_t)(c->min_node_visits + 1) + 1;
+// Nodes one search may allocate (0 for a negative max_playouts): every expanded node first collects
+// min_node_visits + 1 playouts as a leaf, so a search expands at most playouts / (min_node_visits + 1) nodes, each
+// with <= 40 children.
+static size_t tree_capacity(int max_playouts, int min_node_visits) {
+    if (max_playouts < 0) return 0;
+    const size_t exp = (size_t)max_playouts / (size_t)(min_node_visits + 1) + 1;
     return 1 + 40 * exp;
+}
+
+extern "C" size_t oaz_pure_mcts_tree_capacity(const oaz_pure_mcts_config* c) {
+    return c ? tree_capacity(c->max_playouts, c->min_node_visits) : 0;
+}
+
+extern "C" size_t oaz_pure_mcts_each_capacity(const oaz_pure_mcts_root* par, int G, size_t* offsets) {
+    size_t total = 0;
+    for (int g = 0; par && g < G; ++g) {
+        if (offsets) offsets[g] = total;
+        total += par[g].min_node_visits < 0 ? 0 : tree_capacity(par[g].max_playouts, par[g].min_node_visits);
+    }
+    if (offsets && par && G >= 0) offsets[G] = total;
+    return total;
 }
 
 // The search's device buffers as one allocation, and the last one of each device kept for the next call: a
@@ -570,6 +585,114 @@ extern "C" int oaz_pure_mcts_release_workspace(int device) {
     return 0;
 }
 
+// ---- the two searches' common host side ---------------------------------------------------------------------
+namespace {
+// What an entry point has checked and asks run_search for. par, off and out_playouts are
+// oaz_pure_mcts_search_each's (one search per root, bin/mcts_parameter_check.rs's sweep in one launch per ply)
+// and null for oaz_pure_mcts_search.
+struct SearchCall {
+    const char* who = nullptr;  // the error messages' prefix
+    int device = 0, G = 0, max_playouts = 0;  // max_playouts: the call's largest search
+    int64_t search_time_ns = 0;
+    const oaz_state* roots = nullptr;
+    const oaz_pure_mcts_root* par = nullptr;
+    const uint64_t* off = nullptr;  // [G + 1]: the packed trees' offsets
+    size_t nodes = 0;               // all trees together
+    oaz_move* out_move = nullptr;
+    float* out_value = nullptr;
+    int32_t* out_playouts = nullptr;
+    oaz_pure_mcts_stats* stats = nullptr;
+    bool trees = false;  // copy_trees enqueues copies
+};
+
+// The workspace's sections (par, off and po empty without SearchCall::par) and the clock's budget in ticks.
+struct SearchBuffers {
+    oaz_state* roots;
+    oaz_pure_mcts_root* par;
+    uint64_t *off, *st /* [G][8] */;
+    float *ln, *val;
+    oaz_move* mv;
+    int32_t* po;
+    oaz_pure_node* nodes;
+    uint64_t ticks;
+};
+
+// Everything after the argument checks: the device, the ln table, the workspace (the device's kept buffer, shared
+// by both searches), the uploads, launch(buffers, stream), the results and statistics, and the trees that
+// copy_trees(device nodes, stream) enqueues.
+template <class Launch, class CopyTrees>
+int run_search(const SearchCall& c, Launch launch, CopyTrees copy_trees) {
+    const int G = c.G;
+    if (int rc = oaz_check_device(c.who, c.device)) return rc;
+    if (c.device >= kPureMaxDevices) return oaz_set_err(OAZ_ERR_ARG, "%s: device %d unsupported", c.who, c.device);
+    SearchBuffers d{};
+    if (c.search_time_ns > 0) {  // the budget in ticks of the device's constant-rate clock (as oaz_config.search_time_ns)
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c.device) != hipSuccess || khz <= 0)
+            return oaz_set_err(OAZ_ERR_HIP, "%s: search_time: the device reports no wall clock rate", c.who);
+        d.ticks = oaz_budget_ticks(c.search_time_ns, khz, 9e18);
+    }
+    std::vector<float> ln((size_t)c.max_playouts + 2);  // sized by the call's largest search
+    for (size_t n = 0; n < ln.size(); ++n) ln[n] = logf((float)n);  // (parent.visits as f32).ln()
+    auto carve = [&](Carver k) {
+        d.roots = k.take<oaz_state>(G);
+        d.par = k.take<oaz_pure_mcts_root>(c.par ? G : 0);
+        d.off = k.take<uint64_t>(c.par ? (size_t)G + 1 : 0);
+        d.ln = k.take<float>(ln.size());
+        d.val = k.take<float>(G);
+        d.mv = k.take<oaz_move>(G);
+        d.po = k.take<int32_t>(c.par ? G : 0);
+        d.st = k.take<uint64_t>((size_t)8 * G);
+        d.nodes = k.take<oaz_pure_node>(c.nodes);
+        return k.off;
+    };
+    const size_t ws_bytes = carve(Carver{nullptr});
+    // on c.device, on a stream of its own: a search on a worker thread neither lands on the thread's default
+    // device nor waits for (or stalls) the engines searching on the same GPU meanwhile. The stream is declared
+    // after the workspace: on every return it is waited for before the workspace goes back or is freed (and
+    // before `st` goes).
+    OAZ_ON_DEVICE(c.device);
+    std::vector<uint64_t> st((size_t)G * 8);
+    WorkspaceLease ws;
+    Stream sm;
+    if (int rc = sm.create()) return rc;
+    if (int rc = ws.acquire(c.device, ws_bytes)) return rc;
+    carve(Carver{ws.p});
+    HIP_TRY(hipMemcpyAsync(d.roots, c.roots, sizeof(oaz_state) * G, hipMemcpyHostToDevice, sm));
+    if (c.par) {
+        HIP_TRY(hipMemcpyAsync(d.par, c.par, sizeof(oaz_pure_mcts_root) * G, hipMemcpyHostToDevice, sm));
+        HIP_TRY(hipMemcpyAsync(d.off, c.off, sizeof(uint64_t) * ((size_t)G + 1), hipMemcpyHostToDevice, sm));
+    }
+    HIP_TRY(hipMemcpyAsync(d.ln, ln.data(), sizeof(float) * ln.size(), hipMemcpyHostToDevice, sm));
+    launch(d, sm);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(sm));
+    HIP_TRY(hipMemcpyAsync(c.out_move, d.mv, sizeof(oaz_move) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(c.out_value, d.val, sizeof(float) * G, hipMemcpyDeviceToHost, sm));
+    if (c.out_playouts) HIP_TRY(hipMemcpyAsync(c.out_playouts, d.po, sizeof(int32_t) * G, hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(st.data(), d.st, sizeof(uint64_t) * st.size(), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipStreamSynchronize(sm));
+    if (c.stats)  // (zeroed by the entry point)
+        for (int g = 0; g < G; ++g) {
+            const uint64_t* s = &st[(size_t)g * 8];
+            c.stats->playouts += s[0];
+            c.stats->expansions += s[1];
+            c.stats->rollout_plies += s[2];
+            c.stats->rollout_passes += s[3];
+            c.stats->rollouts_capped += s[4];
+            if (s[5] > c.stats->max_nodes) c.stats->max_nodes = s[5];
+            c.stats->tree_full += s[6];
+        }
+    if (c.trees) {
+        if (int rc = copy_trees(d.nodes, sm)) return rc;
+        HIP_TRY(hipStreamSynchronize(sm));
+    }
+    return 0;
+}
+}  // namespace
+
+// Both entry points make every OAZ_ERR_ARG check before the first device query (whether or not a GPU is there),
+// and G == 0 returns before cfg->device is looked at.
 extern "C" int oaz_pure_mcts_search(const oaz_state* roots, int G, const oaz_pure_mcts_config* cfg,
                                     oaz_move* out_move, float* out_value, oaz_pure_mcts_stats* stats,
                                     oaz_pure_node* tree_out, size_t tree_cap) {
@@ -577,95 +700,37 @@ extern "C" int oaz_pure_mcts_search(const oaz_state* roots, int G, const oaz_pur
         return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: null argument");
     if (cfg->max_playouts < 0 || cfg->min_node_visits < 0 || cfg->rollout_cap < 0)
         return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: negative playouts / min_node_visits / rollout_cap");
-    if (int rc = oaz_check_device("pure_mcts", cfg->device)) return rc;
     for (int g = 0; g < G; ++g)
-        if ((roots[g].to_move & ~1) || (roots[g].cards[0] | roots[g].cards[1] | roots[g].cards[2] | roots[g].cards[3] |
-                                        roots[g].cards[4]) > 15)
-            return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: root %d is not a valid state", g);
+        if (!oaz_root_ok(roots[g])) return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: root %d is not a valid state", g);
     if (stats) memset(stats, 0, sizeof(*stats));
     if (G == 0) return 0;
-    const size_t cap = oaz_pure_mcts_tree_capacity(cfg);
+    const size_t cap = tree_capacity(cfg->max_playouts, cfg->min_node_visits);
     if (cap > 0xFFFFFFF0u) return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: tree capacity too large");
-    std::vector<float> ln((size_t)cfg->max_playouts + 2);
-    for (size_t n = 0; n < ln.size(); ++n) ln[n] = logf((float)n);  // (parent.visits as f32).ln()
-    pm::Params p{cfg->max_playouts, cfg->min_node_visits, cfg->rollout_cap, cfg->exploration_c, cfg->seed,
-                 cfg->game_id0, (uint32_t)cap};
-    // the workspace: roots, ln table, values, moves, statistics, trees
-    oaz_state* d_roots = nullptr;
-    float *d_ln = nullptr, *d_val = nullptr;
-    oaz_move* d_mv = nullptr;
-    uint64_t* d_st = nullptr;
-    oaz_pure_node* d_nodes = nullptr;
-    auto carve = [&](Carver c) {
-        d_roots = c.take<oaz_state>(G);
-        d_ln = c.take<float>(ln.size());
-        d_val = c.take<float>(G);
-        d_mv = c.take<oaz_move>(G);
-        d_st = c.take<uint64_t>((size_t)8 * G);
-        d_nodes = c.take<oaz_pure_node>(cap * G);
-        return c.off;
-    };
-    const size_t ws_bytes = carve(Carver{nullptr});
-    // on cfg->device, on a stream of its own: a search on a worker thread neither lands on the thread's
-    // default device nor waits for (or stalls) the engines searching on the same GPU meanwhile. The stream is
-    // declared after the workspace: on every return it is waited for before the workspace goes back or is freed
-    // (and before `st` goes).
-    OAZ_ON_DEVICE(cfg->device);
-    std::vector<uint64_t> st((size_t)G * 8);
-    WorkspaceLease ws;
-    Stream sm;
-    if (int rc = sm.create()) return rc;
-    if (cfg->device >= kPureMaxDevices) return oaz_set_err(OAZ_ERR_ARG, "pure_mcts: device %d unsupported", cfg->device);
-    if (int rc = ws.acquire(cfg->device, ws_bytes)) return rc;
-    carve(Carver{ws.p});
-    HIP_TRY(hipMemcpyAsync(d_roots, roots, sizeof(oaz_state) * G, hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_ln, ln.data(), sizeof(float) * ln.size(), hipMemcpyHostToDevice, sm));
-    hipLaunchKernelGGL(pm::k_pure_mcts, dim3((G + 63) / 64), dim3(64), 0, sm, d_roots, G, p, d_ln, d_nodes, d_mv, d_val,
-                       d_st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(sm));
-    HIP_TRY(hipMemcpyAsync(out_move, d_mv, sizeof(oaz_move) * G, hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(out_value, d_val, sizeof(float) * G, hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(st.data(), d_st, sizeof(uint64_t) * st.size(), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipStreamSynchronize(sm));
-    if (stats)
-        for (int g = 0; g < G; ++g) {
-            stats->playouts += st[g * 8 + 0];
-            stats->expansions += st[g * 8 + 1];
-            stats->rollout_plies += st[g * 8 + 2];
-            stats->rollout_passes += st[g * 8 + 3];
-            stats->rollouts_capped += st[g * 8 + 4];
-            if (st[g * 8 + 5] > stats->max_nodes) stats->max_nodes = st[g * 8 + 5];
-            stats->tree_full += st[g * 8 + 6];
-        }
-    if (tree_out && tree_cap) {
-        for (int g = 0; g < G; ++g)
-            HIP_TRY(hipMemcpyAsync(tree_out + (size_t)g * tree_cap, d_nodes + (size_t)g * cap,
-                                   sizeof(oaz_pure_node) * (tree_cap < cap ? tree_cap : cap), hipMemcpyDeviceToHost, sm));
-        HIP_TRY(hipStreamSynchronize(sm));
-    }
-    return 0;
-}
-
-// ---- one search per root, each with its own parameters (bin/mcts_parameter_check.rs's sweep in one launch per ply) --
-namespace {
-size_t each_root_capacity(const oaz_pure_mcts_root& r) {  // oaz_pure_mcts_tree_capacity of (max_playouts, min_node_visits)
-    if (r.max_playouts < 0 || r.min_node_visits < 0) return 0;
-    oaz_pure_mcts_config c{};
-    c.max_playouts = r.max_playouts;
-    c.min_node_visits = r.min_node_visits;
-    return oaz_pure_mcts_tree_capacity(&c);
-}
-}  // namespace
-
-extern "C" size_t oaz_pure_mcts_each_capacity(const oaz_pure_mcts_root* par, int G, size_t* offsets) {
-    size_t total = 0;
-    for (int g = 0; par && g < G; ++g) {
-        if (offsets) offsets[g] = total;
-        total += each_root_capacity(par[g]);
-    }
-    if (offsets && par && G >= 0) offsets[G] = total;
-    return total;
+    const pm::Params p{cfg->max_playouts, cfg->min_node_visits, cfg->rollout_cap, cfg->exploration_c, cfg->seed,
+                       cfg->game_id0, (uint32_t)cap};
+    SearchCall c;
+    c.who = "pure_mcts";
+    c.device = cfg->device;
+    c.G = G;
+    c.max_playouts = cfg->max_playouts;
+    c.roots = roots;
+    c.nodes = cap * G;
+    c.out_move = out_move;
+    c.out_value = out_value;
+    c.stats = stats;
+    c.trees = tree_out && tree_cap;
+    return run_search(
+        c,
+        [&](const SearchBuffers& d, hipStream_t sm) {
+            hipLaunchKernelGGL(pm::k_pure_mcts, dim3((G + 63) / 64), dim3(64), 0, sm, d.roots, G, p, d.ln, d.nodes, d.mv,
+                               d.val, d.st);
+        },
+        [&](const oaz_pure_node* d_nodes, hipStream_t sm) {
+            for (int g = 0; g < G; ++g)
+                HIP_TRY(hipMemcpyAsync(tree_out + (size_t)g * tree_cap, d_nodes + (size_t)g * cap,
+                                       sizeof(oaz_pure_node) * (tree_cap < cap ? tree_cap : cap), hipMemcpyDeviceToHost, sm));
+            return 0;
+        });
 }
 
 extern "C" int oaz_pure_mcts_search_each(const oaz_state* roots, const oaz_pure_mcts_root* par, int G,
@@ -685,10 +750,8 @@ extern "C" int oaz_pure_mcts_search_each(const oaz_state* roots, const oaz_pure_
         if (par[g].stream >> 32)
             return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d: stream %llu is not below 2^32", g,
                                (unsigned long long)par[g].stream);
-        if ((roots[g].to_move & ~1) || (roots[g].cards[0] | roots[g].cards[1] | roots[g].cards[2] | roots[g].cards[3] |
-                                        roots[g].cards[4]) > 15)
-            return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d is not a valid state", g);
-        if (each_root_capacity(par[g]) > 0xFFFFFFF0u)
+        if (!oaz_root_ok(roots[g])) return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d is not a valid state", g);
+        if (tree_capacity(par[g].max_playouts, par[g].min_node_visits) > 0xFFFFFFF0u)
             return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d: tree capacity too large", g);
         if (tree_out && tree_offsets[g + 1] < tree_offsets[g])
             return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: root %d: tree_offsets decrease", g);
@@ -696,90 +759,44 @@ extern "C" int oaz_pure_mcts_search_each(const oaz_state* roots, const oaz_pure_
     }
     if (stats) memset(stats, 0, sizeof(*stats));
     if (G == 0) return 0;
-    if (int rc = oaz_check_device("pure_mcts_each", cfg->device)) return rc;
-    if (cfg->device >= kPureMaxDevices)
-        return oaz_set_err(OAZ_ERR_ARG, "pure_mcts_each: device %d unsupported", cfg->device);
     std::vector<uint64_t> off((size_t)G + 1);
     const size_t total = oaz_pure_mcts_each_capacity(par, G, reinterpret_cast<size_t*>(off.data()));
-    std::vector<float> ln((size_t)max_playouts + 2);  // sized by the call's largest search
-    for (size_t n = 0; n < ln.size(); ++n) ln[n] = logf((float)n);
-    pm::EachParams p{cfg->rollout_cap, cfg->search_time_ns > 0 ? 1 : 0, cfg->seed, 0};
-    if (p.clock_on) {  // the budget in ticks of the device's constant-rate clock (as oaz_config.search_time_ns)
-        int khz = 0;
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, cfg->device) != hipSuccess || khz <= 0)
-            return oaz_set_err(OAZ_ERR_HIP, "pure_mcts_each: search_time: the device reports no wall clock rate");
-        const double ticks = (double)cfg->search_time_ns * (double)khz * 1e-6;
-        p.ticks = ticks < 9e18 ? (uint64_t)ticks : (uint64_t)9e18;
-    }
-    // the workspace (the device's kept buffer, shared with oaz_pure_mcts_search): roots, parameters, tree offsets,
-    // ln table, values, moves, playouts, statistics, and the trees packed by `off`
-    oaz_state* d_roots = nullptr;
-    oaz_pure_mcts_root* d_par = nullptr;
-    uint64_t *d_off = nullptr, *d_st = nullptr;
-    float *d_ln = nullptr, *d_val = nullptr;
-    oaz_move* d_mv = nullptr;
-    int32_t* d_po = nullptr;
-    oaz_pure_node* d_nodes = nullptr;
-    auto carve = [&](Carver c) {
-        d_roots = c.take<oaz_state>(G);
-        d_par = c.take<oaz_pure_mcts_root>(G);
-        d_off = c.take<uint64_t>((size_t)G + 1);
-        d_ln = c.take<float>(ln.size());
-        d_val = c.take<float>(G);
-        d_mv = c.take<oaz_move>(G);
-        d_po = c.take<int32_t>(G);
-        d_st = c.take<uint64_t>((size_t)8 * G);
-        d_nodes = c.take<oaz_pure_node>(total);
-        return c.off;
-    };
-    const size_t ws_bytes = carve(Carver{nullptr});
-    OAZ_ON_DEVICE(cfg->device);
-    std::vector<uint64_t> st((size_t)G * 8);
-    std::vector<int32_t> po((size_t)G);
-    WorkspaceLease ws;  // (declared before the stream: waited for before the workspace goes back, as above)
-    Stream sm;
-    if (int rc = sm.create()) return rc;
-    if (int rc = ws.acquire(cfg->device, ws_bytes)) return rc;
-    carve(Carver{ws.p});
-    HIP_TRY(hipMemcpyAsync(d_roots, roots, sizeof(oaz_state) * G, hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_par, par, sizeof(oaz_pure_mcts_root) * G, hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_off, off.data(), sizeof(uint64_t) * off.size(), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(d_ln, ln.data(), sizeof(float) * ln.size(), hipMemcpyHostToDevice, sm));
-    hipLaunchKernelGGL(pm::k_pure_mcts_each, dim3((G + 63) / 64), dim3(64), 0, sm, d_roots, d_par, d_off, G, p, d_ln,
-                       d_nodes, d_mv, d_val, d_po, d_st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(sm));
-    HIP_TRY(hipMemcpyAsync(out_move, d_mv, sizeof(oaz_move) * G, hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(out_value, d_val, sizeof(float) * G, hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(po.data(), d_po, sizeof(int32_t) * G, hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipMemcpyAsync(st.data(), d_st, sizeof(uint64_t) * st.size(), hipMemcpyDeviceToHost, sm));
-    HIP_TRY(hipStreamSynchronize(sm));
-    if (out_playouts) memcpy(out_playouts, po.data(), sizeof(int32_t) * G);
-    if (stats)
-        for (int g = 0; g < G; ++g) {
-            stats->playouts += st[g * 8 + 0];
-            stats->expansions += st[g * 8 + 1];
-            stats->rollout_plies += st[g * 8 + 2];
-            stats->rollout_passes += st[g * 8 + 3];
-            stats->rollouts_capped += st[g * 8 + 4];
-            if (st[g * 8 + 5] > stats->max_nodes) stats->max_nodes = st[g * 8 + 5];
-            stats->tree_full += st[g * 8 + 6];
-        }
-    if (tree_out) {
-        // root g's nodes go to tree_out + tree_offsets[g], as many as its slice there holds; with the offsets of
-        // oaz_pure_mcts_each_capacity that is the packed device array as it stands
-        bool same = true;
-        for (int g = 0; g <= G && same; ++g) same = tree_offsets[g] == off[g];
-        if (same) {
-            HIP_TRY(hipMemcpyAsync(tree_out, d_nodes, sizeof(oaz_pure_node) * total, hipMemcpyDeviceToHost, sm));
-        } else {
+    SearchCall c;
+    c.who = "pure_mcts_each";
+    c.device = cfg->device;
+    c.G = G;
+    c.max_playouts = max_playouts;
+    c.search_time_ns = cfg->search_time_ns;
+    c.roots = roots;
+    c.par = par;
+    c.off = off.data();
+    c.nodes = total;
+    c.out_move = out_move;
+    c.out_value = out_value;
+    c.out_playouts = out_playouts;
+    c.stats = stats;
+    c.trees = tree_out != nullptr;
+    return run_search(
+        c,
+        [&](const SearchBuffers& d, hipStream_t sm) {
+            const pm::EachParams p{cfg->rollout_cap, cfg->search_time_ns > 0 ? 1 : 0, cfg->seed, d.ticks};
+            hipLaunchKernelGGL(pm::k_pure_mcts_each, dim3((G + 63) / 64), dim3(64), 0, sm, d.roots, d.par, d.off, G, p,
+                               d.ln, d.nodes, d.mv, d.val, d.po, d.st);
+        },
+        [&](const oaz_pure_node* d_nodes, hipStream_t sm) {
+            // root g's nodes go to tree_out + tree_offsets[g], as many as its slice there holds; with the offsets of
+            // oaz_pure_mcts_each_capacity that is the packed device array as it stands
+            bool same = true;
+            for (int g = 0; g <= G && same; ++g) same = tree_offsets[g] == off[g];
+            if (same) {
+                HIP_TRY(hipMemcpyAsync(tree_out, d_nodes, sizeof(oaz_pure_node) * total, hipMemcpyDeviceToHost, sm));
+                return 0;
+            }
             for (int g = 0; g < G; ++g) {
                 const size_t have = off[g + 1] - off[g], room = tree_offsets[g + 1] - tree_offsets[g];
                 HIP_TRY(hipMemcpyAsync(tree_out + tree_offsets[g], d_nodes + off[g],
                                        sizeof(oaz_pure_node) * (room < have ? room : have), hipMemcpyDeviceToHost, sm));
             }
-        }
-        HIP_TRY(hipStreamSynchronize(sm));
-    }
-    return 0;
+            return 0;
+        });
 }

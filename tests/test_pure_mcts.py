@@ -66,6 +66,54 @@ def test_oracle_tree_invariants(orc):
                 assert n["winrate"] == np.float32(n["reward"]) / np.float32(n["visits"])
 
 
+def _raw_call(lib, roots, cfg, G=None, null=()):
+    G = len(roots) if G is None else G
+    mv, val = np.zeros(max(G, 1), dtype=_abi.MOVE_DTYPE), np.zeros(max(G, 1), dtype=np.float32)
+    st = _abi.oaz_pure_mcts_stats()
+    st.playouts = 7
+    rc = lib.oaz_pure_mcts_search(
+        None if "roots" in null else _abi.ptr(roots), G, None if "cfg" in null else C.byref(cfg),
+        None if "out_move" in null else _abi.ptr(mv), None if "out_value" in null else _abi.ptr(val), C.byref(st),
+        None, 0)
+    return rc, (lib.oaz_last_error() or b"").decode(), st
+
+
+def test_argument_checks_come_before_any_device(lib, orc):
+    """Every OAZ_ERR_ARG case of oaz_pure_mcts_search returns -1 whether or not a GPU is there, and names the
+    root it is about (test_pure_mcts_each.py's test of oaz_pure_mcts_search_each, for this entry point)."""
+    roots = random_positions(orc, 3, seed=5)
+    for name in ("roots", "cfg", "out_move", "out_value"):
+        rc, msg, _ = _raw_call(lib, roots, _cfg(10, 1), null=(name,))
+        assert rc == _abi.ERR_ARG and "null" in msg, name
+    rc, msg, _ = _raw_call(lib, roots, _cfg(10, 1), G=-1)
+    assert rc == _abi.ERR_ARG and msg == "pure_mcts: null argument", msg  # (the G < 0 check's message)
+    for field in ("max_playouts", "min_node_visits", "rollout_cap"):
+        cfg = _cfg(10, 1)
+        setattr(cfg, field, -1)
+        rc, msg, _ = _raw_call(lib, roots, cfg)
+        assert rc == _abi.ERR_ARG and "negative" in msg, (field, msg)
+    for bad in ("to_move", "cards", "squares"):
+        # squares: one bit outside the 25 squares (the low 7 bits) in each of the four bitboards in turn
+        for board, side, bit in ((None, 0, 0),) if bad != "squares" else (
+                ("kings", 0, 0), ("kings", 1, 6), ("pawns", 0, 3), ("pawns", 1, 5)):
+            broken = roots.copy()
+            if bad == "to_move":
+                broken["to_move"][2] = 2
+            elif bad == "cards":
+                broken["cards"][2][3] = 16
+            else:
+                broken[board][2][side] |= 1 << bit
+            rc, msg, _ = _raw_call(lib, broken, _cfg(10, 1))
+            assert rc == _abi.ERR_ARG and "root 2 is not a valid state" in msg, (bad, board, side, msg)
+
+
+def test_no_roots_is_ok_and_touches_no_device(lib):
+    cfg = _cfg(10, 1)
+    cfg.device = 12345  # never looked at
+    rc, _, st = _raw_call(lib, None, cfg, G=0, null=("roots", "out_move", "out_value"))
+    assert rc == 0 and st.playouts == 0 and st.max_nodes == 0
+
+
 @pytest.mark.gpu
 def test_gpu_trees_bitexact_vs_oracle(orc):
     from onitama_az.pure_mcts import pure_mcts_search

@@ -136,14 +136,19 @@ def test_argument_checks_come_before_any_device(lib, orc):
     assert rc == _abi.ERR_ARG and "rollout_cap" in msg, msg
     rc, msg, _ = _raw_call(lib, roots, good, cfg(search_time_ns=-1))
     assert rc == _abi.ERR_ARG and "search_time_ns" in msg, msg
-    for bad in ("to_move", "cards"):
-        broken = roots.copy()
-        if bad == "to_move":
-            broken["to_move"][2] = 2
-        else:
-            broken["cards"][2][3] = 16
-        rc, msg, _ = _raw_call(lib, broken, good, cfg())
-        assert rc == _abi.ERR_ARG and "root 2 is not a valid state" in msg, (bad, msg)
+    for bad in ("to_move", "cards", "squares"):
+        # squares: one bit outside the 25 squares (the low 7 bits) in each of the four bitboards in turn
+        for board, side, bit in ((None, 0, 0),) if bad != "squares" else (
+                ("kings", 0, 0), ("kings", 1, 6), ("pawns", 0, 3), ("pawns", 1, 5)):
+            broken = roots.copy()
+            if bad == "to_move":
+                broken["to_move"][2] = 2
+            elif bad == "cards":
+                broken["cards"][2][3] = 16
+            else:
+                broken[board][2][side] |= 1 << bit
+            rc, msg, _ = _raw_call(lib, broken, good, cfg())
+            assert rc == _abi.ERR_ARG and "root 2 is not a valid state" in msg, (bad, board, side, msg)
     rc, msg, _ = _raw_call(lib, roots, good, cfg(), tree=np.zeros(4096, dtype=_abi.PURE_NODE_DTYPE))
     assert rc == _abi.ERR_ARG and "tree_offsets" in msg, msg
 
@@ -190,6 +195,24 @@ def test_gpu_uniform_parameters_equal_the_existing_entry_point(orc):
             assert n > 1 and new.tree(g)[:n].tobytes() == old.trees[g][:n].tobytes(), (g, min_visits)
         assert (new.stats.playouts, new.stats.expansions, new.stats.rollout_plies, new.stats.max_nodes) == (
             old.stats.playouts, old.stats.expansions, old.stats.rollout_plies, old.stats.max_nodes)
+
+
+@pytest.mark.gpu
+def test_gpu_one_wave_and_one_lane_equal_the_existing_entry_point(orc):
+    """65 roots: one full wave and one lane in a second block, so both kernels meet their `g >= G` guard and the
+    last lane's tree offset (tree 64 of either layout)."""
+    from onitama_az.pure_mcts import pure_mcts_search, pure_mcts_search_each
+    G, po, min_visits = 65, 60, 1
+    roots = random_positions(orc, G, seed=79)
+    old = pure_mcts_search(roots, po, min_visits, SQRT2, seed=SEED, game_id0=2000, with_trees=True)
+    new = pure_mcts_search_each(roots, po, min_visits, SQRT2, 2000 + np.arange(G), seed=SEED, with_trees=True)
+    assert new.moves.tobytes() == old.moves.tobytes() and new.values.tobytes() == old.values.tobytes()
+    for g in range(G):
+        n = _node_count(old.trees[g])
+        assert n > 1 and new.tree(g)[:n].tobytes() == old.trees[g][:n].tobytes(), g
+    fields = ("playouts", "expansions", "rollout_plies", "rollout_passes", "rollouts_capped", "max_nodes", "tree_full")
+    assert [getattr(new.stats, f) for f in fields] == [getattr(old.stats, f) for f in fields]
+    assert new.playouts.tolist() == [po] * G and old.stats.playouts == po * G
 
 
 @pytest.mark.gpu
