@@ -873,6 +873,41 @@ int oaz_arena_fight_slots(const oaz_arena_config* cfg, int32_t slots, const oaz_
                           oaz_fight_stats* stats, uint8_t* results, int32_t* plies, double* history,
                           oaz_arena_slots_stats* slot_stats);
 
+/* ---- left-right reflection ---------------------------------------------------------
+ * Onitama is invariant under the reflection in the c-file when every card is replaced by its reflected card: the
+ * start position (state.rs:24-45), the temples (state.rs:48-49: c5 and c1) and the rules are symmetric, and the
+ * attack maps obey reflect(ATTACK_MAPS[c][k][f]) == ATTACK_MAPS[c][C[k]][R(f)] (card.rs:476-604). Neither the
+ * reference nor its training loop uses this; it is what doubles a self-play buffer for free.
+ *   square   R(i) = 5 * (i / 5) + 4 - i % 5 for i < 25; R(25) = 25 (the pass move's from = to = 25)
+ *   bitboard the bit of square i (1u << (31 - i), common/mod.rs:2-16) moves to the bit of R(i); bits 6..0 stay
+ *   card     C = 0 1 3 2 4 5 7 6 8 9 10 12 11 13 15 14 (ORIGINAL_CARDS order, card.rs:465-468): Frog<->Rabbit,
+ *            Goose<->Rooster, Horse<->Ox, Eel<->Cobra, the other eight fixed; derived at compile time from the
+ *            attack table as the unique card obeying the law
+ *   state    kings[c], pawns[c] reflected, cards[k] = C[cards[k]] in the same deck slot (deck.rs:14-18); to_move
+ *            and pad unchanged
+ *   move     from and to through R; piece and slot unchanged (a reflected card keeps its slot)
+ *   sample   the state as above; pi'[k * 25 + R(t)] = pi[k * 25 + t] for k = 0, 1 (pi is keyed by hand slot and
+ *            `to`, calculate_priors, mcts_arena.rs:104-124); z unchanged. Bytes are moved, never recomputed:
+ *            applying the transformation twice returns the input byte for byte.
+ * Host helpers (no GPU). out == in is allowed; n == 0 is OAZ_OK. A card id >= 16 or a square > 25 in any element
+ * is OAZ_ERR_ARG (as a null pointer or n < 0), and nothing is written then. */
+int oaz_reflect_card(int card);   /* C[card]; -1 outside 0..15 */
+int oaz_reflect_states_host(const oaz_state* in, int n, oaz_state* out);
+int oaz_reflect_moves_host(const oaz_move* in, int n, oaz_move* out);
+int oaz_reflect_samples_host(const oaz_sample* in, size_t n, oaz_sample* out);
+/* The same as oaz_reflect_samples_host on the GPU (host pointers, the thread's current device, as oaz_encode):
+ * the records go through device scratch buffers and one kernel whose lanes stride over the 57 words of
+ * consecutive records. The same argument checks, made on the host before a device is touched. */
+int oaz_reflect_samples(const oaz_sample* in, size_t n, oaz_sample* out);
+/* oaz_trainer_set_batches with a flag per index entry (n_batches x batch bytes, 0 or 1; NULL = all 0, which is
+ * oaz_trainer_set_batches): a flagged entry makes the step's gather produce the input planes, pi row and z of
+ * the reflected sample (create_tensor_from_state, common.rs:26-80, of the reflected state), inside the one
+ * gather launch and without a reflected copy of the buffer, on owned and on bound samples (which are only read)
+ * and on every step path (backward, apply, train). A flag other than 0 or 1 is OAZ_ERR_ARG, as a bad index is,
+ * and leaves the uploaded batches as they were. Sample indices must then be below 2^31, which int32 makes them. */
+int oaz_trainer_set_batches_reflect(oaz_trainer* t, const int32_t* idx, const uint8_t* reflect, int n_batches,
+                                    int batch);
+
 #ifdef __cplusplus
 }
 #endif

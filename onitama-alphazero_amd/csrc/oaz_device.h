@@ -355,6 +355,87 @@ OAZ_HD int temperature_draw_child(uint64_t seed, uint64_t game, uint32_t ply, co
     return -1;  // (never reached: r < S)
 }
 
+// ---- left-right reflection -------------------------------------------------------
+// The reflection in the c-file: square i -> R(i) = 5 (i / 5) + 4 - i % 5, and card k -> C[k], the card whose
+// attack map is the reflected one: reflect_bits(ATTACK[c][k][f]) == ATTACK[c][C[k]][R(f)] for both colours and
+// all 25 squares. The rules commute with it (start position, temples and attack maps are symmetric; the law is
+// checked against the oracle in tests/test_reflect.py), so a self-play record (s, pi, z) has the equally valid
+// record (R s, R pi, z). One body for the host entries (oaz_reflect_*_host), k_reflect_samples and the trainer's
+// gather (k_gather): a permutation of bits and bytes with no arithmetic in it.
+OAZ_HD constexpr int reflect_sq(int i) { return i < 25 ? i + 4 - 2 * (i % 5) : i; }  // 25 (the pass move) is fixed
+// columns a..e of every row; bits 6..0 are no squares and stay where they are
+OAZ_HD constexpr uint32_t reflect_bits(uint32_t b) {
+    constexpr uint32_t a = 0x84210800u;  // the a-file: squares 0, 5, 10, 15, 20
+    return ((b & a) >> 4) | ((b & (a >> 4)) << 4) | ((b & (a >> 1)) >> 2) | ((b & (a >> 3)) << 2) |
+           (b & ((a >> 2) | 0x7Fu));
+}
+// C, derived from the attack table: nibble k of the result is the unique k' with the law above. 0 when some card
+// has no partner or more than one (the static_assert below then fails).
+constexpr uint64_t make_reflect_cards() {
+    uint64_t packed = 0;
+    for (int k = 0; k < 16; ++k) {
+        int found = -1, n = 0;
+        for (int k2 = 0; k2 < 16; ++k2) {
+            bool same = true;
+            for (int color = 0; color < 2 && same; ++color)
+                for (int f = 0; f < 25 && same; ++f)
+                    same = reflect_bits(kAttackHost.m[color][k][f]) == kAttackHost.m[color][k2][reflect_sq(f)];
+            if (same) {
+                found = k2;
+                ++n;
+            }
+        }
+        if (n != 1) return 0;
+        packed |= (uint64_t)found << (4 * k);
+    }
+    return packed;
+}
+constexpr uint64_t kReflectCards = make_reflect_cards();  // 16 nibbles: a scalar, so device code reads no table
+OAZ_HD constexpr int reflect_card(int k) { return (int)((kReflectCards >> (4 * (k & 15))) & 15u); }
+constexpr bool reflect_cards_involution() {
+    for (int k = 0; k < 16; ++k)
+        if (reflect_card(reflect_card(k)) != k) return false;
+    return true;
+}
+static_assert(reflect_cards_involution(), "the card reflection must be an involution");
+// 0 Tiger 1 Dragon 3 Rabbit 2 Frog 4 Crab 5 Elephant 7 Rooster 6 Goose 8 Monkey 9 Mantis 10 Crane 12 Ox 11 Horse
+// 13 Boar 15 Cobra 14 Eel
+static_assert(kReflectCards == 0xEFDBCA9867542310ull, "Frog<->Rabbit, Goose<->Rooster, Horse<->Ox, Eel<->Cobra");
+
+// the four card bytes of one little-endian word (oaz_state.cards[0..3]); nbytes = 1 for the word that holds
+// cards[4], to_move and pad, whose upper bytes stay
+OAZ_HD uint32_t reflect_card_word(uint32_t w, int nbytes) {
+    uint32_t out = w;
+    for (int i = 0; i < nbytes; ++i) {
+        const uint32_t c = (w >> (8 * i)) & 0xFFu;
+        out = (out & ~(0xFFu << (8 * i))) | ((uint32_t)reflect_card((int)c) << (8 * i));
+    }
+    return out;
+}
+OAZ_HD void reflect_state(const oaz_state& in, oaz_state& out) {
+    oaz_state s = in;
+    for (int c = 0; c < 2; ++c) {
+        s.kings[c] = reflect_bits(in.kings[c]);
+        s.pawns[c] = reflect_bits(in.pawns[c]);
+    }
+    for (int k = 0; k < 5; ++k) s.cards[k] = (uint8_t)reflect_card(in.cards[k]);
+    out = s;
+}
+OAZ_HD bool reflect_state_ok(const oaz_state& s) {  // what reflect_card is defined on
+    return s.cards[0] < 16 && s.cards[1] < 16 && s.cards[2] < 16 && s.cards[3] < 16 && s.cards[4] < 16;
+}
+// A record as 57 little-endian words: 0-3 the bitboards, 4 cards[0..3], 5 cards[4] | to_move | pad, 6-55 pi
+// [2][25], 56 z. Word d of the reflected record is a function of one word of the record: which one,
+constexpr int kSampleWords = 57;
+static_assert(sizeof(oaz_sample) == 4 * kSampleWords && sizeof(oaz_state) == 24, "oaz_sample is 57 words");
+OAZ_HD int reflect_sample_src(int d) {  // pi'[k][t] = pi[k][R(t)] (R is an involution); every other word stays
+    return (d >= 6 && d < 56) ? 6 + ((d - 6) / 25) * 25 + reflect_sq((d - 6) % 25) : d;
+}
+// ... and what becomes of it
+OAZ_HD uint32_t reflect_sample_word(int d, uint32_t w) {
+    return d < 4 ? reflect_bits(w) : d == 4 ? reflect_card_word(w, 4) : d == 5 ? reflect_card_word(w, 1) : w;
+}
+
 OAZ_HD uint64_t splitmix64(uint64_t x) {
     uint64_t z = x + 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

@@ -154,6 +154,55 @@ extern "C" void oaz_hash_eval(const oaz_state* s, float policy[50], float* value
     *value = hash_value(h);
 }
 
+// ---- left-right reflection on the host (oaz_device.h "left-right reflection") --------------------
+extern "C" int oaz_reflect_card(int card) { return card < 0 || card > 15 ? -1 : reflect_card(card); }
+
+static bool reflect_states_ok(const oaz_state* s, size_t n, size_t stride) {
+    for (size_t i = 0; i < n; ++i)
+        if (!reflect_state_ok(*reinterpret_cast<const oaz_state*>(reinterpret_cast<const char*>(s) + i * stride)))
+            return false;
+    return true;
+}
+
+extern "C" int oaz_reflect_states_host(const oaz_state* in, int n, oaz_state* out) {
+    if (!in || !out || n < 0) return oaz_set_err(OAZ_ERR_ARG, "reflect_states: bad arguments");
+    if (!reflect_states_ok(in, (size_t)n, sizeof(oaz_state)))
+        return oaz_set_err(OAZ_ERR_ARG, "reflect_states: a card id is not below 16");
+    for (int i = 0; i < n; ++i) reflect_state(in[i], out[i]);
+    return 0;
+}
+
+extern "C" int oaz_reflect_moves_host(const oaz_move* in, int n, oaz_move* out) {
+    if (!in || !out || n < 0) return oaz_set_err(OAZ_ERR_ARG, "reflect_moves: bad arguments");
+    for (int i = 0; i < n; ++i)
+        if (in[i].from > 25 || in[i].to > 25) return oaz_set_err(OAZ_ERR_ARG, "reflect_moves: move %d: square above 25", i);
+    for (int i = 0; i < n; ++i) {
+        oaz_move m = in[i];
+        m.from = (uint8_t)reflect_sq(m.from);
+        m.to = (uint8_t)reflect_sq(m.to);
+        out[i] = m;
+    }
+    return 0;
+}
+
+static int reflect_samples_check(const oaz_sample* in, size_t n, const oaz_sample* out) {
+    if (!in || !out) return oaz_set_err(OAZ_ERR_ARG, "reflect_samples: null pointer");
+    if (!reflect_states_ok(&in->state, n, sizeof(oaz_sample)))
+        return oaz_set_err(OAZ_ERR_ARG, "reflect_samples: a card id is not below 16");
+    return 0;
+}
+
+extern "C" int oaz_reflect_samples_host(const oaz_sample* in, size_t n, oaz_sample* out) {
+    if (int rc = reflect_samples_check(in, n, out)) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t w[kSampleWords], r[kSampleWords];  // a copy first: out may be in
+        memcpy(w, &in[i], sizeof(w));
+        for (int d = 0; d < kSampleWords; ++d) r[d] = reflect_sample_word(d, w[reflect_sample_src(d)]);
+        memcpy(&out[i], r, sizeof(r));
+    }
+    return 0;
+}
+
 // ---- rules context (no engine needed) ----------------------------------------------------------
 // One context per device (stream + scratch buffers allocated on that device): the rules entry points run
 // on the calling thread's current device, so calls from threads on different GPUs never share buffers.
@@ -165,6 +214,7 @@ struct RulesCtx {
     DevBuf<uint32_t> b;   // move masks or input planes (4-byte words),
     DevBuf<oaz_move> c;   // moves,
     DevBuf<uint8_t> d;    // move counts or results
+    DevBuf<oaz_sample> e, f;  // records in and out (oaz_reflect_samples)
 };
 constexpr int kRulesMaxDevices = 64;
 // never deleted: no hipFree or hipStreamDestroy while the HIP runtime unloads at process exit (oaz_host.h)
@@ -259,6 +309,23 @@ extern "C" int oaz_encode(const oaz_state* s, int n, float* planes) {
     HIP_TRY(hipMemcpyAsync(R->a, s, (size_t)n * sizeof(oaz_state), hipMemcpyHostToDevice, st));
     HIP_TRY(launch_encode(R->a, n, (float*)R->b.get(), st));
     HIP_TRY(hipMemcpyAsync(planes, R->b, (size_t)n * 525 * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int oaz_reflect_samples(const oaz_sample* in, size_t n, oaz_sample* out) {
+    if (int rc = reflect_samples_check(in, n, out)) return rc;
+    if (n == 0) return 0;
+    if (!launch_reflect_samples) return oaz_set_err(OAZ_ERR_STATE, "reflect_samples: built without its kernel");
+    RulesCtx* R = nullptr;
+    std::unique_lock<std::mutex> lk;
+    if (int rc = rules_begin(&R, lk)) return rc;
+    hipStream_t st = R->stream;
+    if (int rc = R->e.reserve(n)) return rc;
+    if (int rc = R->f.reserve(n)) return rc;
+    HIP_TRY(hipMemcpyAsync(R->e, in, n * sizeof(oaz_sample), hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_reflect_samples(R->e, n, R->f, st));
+    HIP_TRY(hipMemcpyAsync(out, R->f, n * sizeof(oaz_sample), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

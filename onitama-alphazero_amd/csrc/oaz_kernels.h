@@ -113,6 +113,9 @@ hipError_t launch_movegen(const oaz_state* s, int n, uint32_t* masks, oaz_move* 
 hipError_t launch_step(oaz_state* s, const oaz_move* mv, int n, uint8_t* results, hipStream_t st);
 hipError_t launch_current_state(const oaz_state* s, int n, uint8_t* results, hipStream_t st);
 hipError_t launch_encode(const oaz_state* s, int n, float* planes, hipStream_t st);
+// out[i] = the reflected in[i] (oaz_device.h "left-right reflection"); out must not overlap in. Weak as the
+// launchers below: the engine's host code also links against stand-in launchers that do not know this one.
+__attribute__((weak)) hipError_t launch_reflect_samples(const oaz_sample* in, size_t n, oaz_sample* out, hipStream_t st);
 
 // evaluators
 hipError_t launch_nn_forward(const NNView& w, const oaz_state* s, int B, float* policy,

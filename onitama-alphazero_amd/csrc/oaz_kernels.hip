@@ -198,6 +198,19 @@ __global__ void k_encode(const oaz_state* states, int n, float* planes) {
     planes[i] = v;
 }
 
+// The reflected records (oaz_device.h "left-right reflection"): one thread per 4-byte word of the output,
+// consecutive lanes on consecutive words of consecutive records (a record is 57 words), so a wave's stores are
+// one contiguous 256 bytes and its loads stay inside the same one or two records (a pi word comes from the same
+// 5-word board row). Grid-stride in 64 bits: n * 57 may pass 2^32. out must not overlap in.
+__global__ void __launch_bounds__(256) k_reflect_samples(const uint32_t* in, size_t n, uint32_t* out) {
+    const size_t total = n * (size_t)kSampleWords, step = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const size_t rec = i / kSampleWords;
+        const int d = (int)(i - rec * kSampleWords);
+        out[i] = reflect_sample_word(d, in[rec * kSampleWords + reflect_sample_src(d)]);
+    }
+}
+
 __global__ void k_hash_eval(const oaz_state* states, int n, float* policy, float* value) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1625,6 +1638,13 @@ hipError_t launch_current_state(const oaz_state* s, int n, uint8_t* results, hip
 hipError_t launch_encode(const oaz_state* s, int n, float* planes, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_encode, dim3(thread_grid((long long)n * 525, 256)), dim3(256), 0, st, s, n, planes);
+    return hipGetLastError();
+}
+hipError_t launch_reflect_samples(const oaz_sample* in, size_t n, oaz_sample* out, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const size_t blocks = (n * (size_t)kSampleWords + 255) / 256;  // at most 8192 workgroups, each striding on
+    hipLaunchKernelGGL(k_reflect_samples, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st,
+                       reinterpret_cast<const uint32_t*>(in), n, reinterpret_cast<uint32_t*>(out));
     return hipGetLastError();
 }
 hipError_t launch_hash_eval(const oaz_state* s, int B, float* policy, float* value, hipStream_t st) {

@@ -63,6 +63,11 @@ __device__ __forceinline__ float wave_sum(float v) {
 // ---- gather: create_tensor_from_state (common.rs:26-80) for samples[idx[b]] ----------------------
 // threads [0, R): one input row (square, sample); [R, R + 50B): pi; [R + 50B, R + 51B): z
 // bi: the batch number, or -1: the one kept on the device (*cur, advanced by the graph replay)
+// An index entry with bit 31 (kGatherReflect) set stands for the reflected sample (oaz_device.h "left-right
+// reflection", oaz_trainer_set_batches_reflect): its row of square sq is the sample's row of R(sq) with the two
+// hand cards replaced by their reflected cards, its pi[k][t] the sample's pi[k][R(t)], its z the sample's. The
+// samples are only read; without the bit every output is what it was.
+constexpr uint32_t kGatherReflect = 0x80000000u;
 __global__ void k_gather(const oaz_sample* samples, const int32_t* idx_all, const int32_t* cur, int bi, int B,
                          float* X0, float* pi, float* z) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -70,14 +75,19 @@ __global__ void k_gather(const oaz_sample* samples, const int32_t* idx_all, cons
     const int32_t* idx = idx_all + (size_t)(bi >= 0 ? bi : *cur) * B;
     if (t >= R) {
         const int u = t - R;
-        if (u < B * 50) pi[u] = samples[idx[u / 50]].pi[u % 50];
-        else if (u < B * 51) z[u - B * 50] = samples[idx[u - B * 50]].z;
+        if (u < B * 50) {
+            const uint32_t e = (uint32_t)idx[u / 50];
+            const int j = u % 50;
+            pi[u] = samples[e & ~kGatherReflect].pi[(e & kGatherReflect) ? (j / 25) * 25 + reflect_sq(j % 25) : j];
+        } else if (u < B * 51) z[u - B * 50] = samples[(uint32_t)idx[u - B * 50] & ~kGatherReflect].z;
         return;
     }
     const int b = t % B, sq = t / B;
-    const oaz_state st = samples[idx[b]].state;
+    const uint32_t e = (uint32_t)idx[b];
+    const bool refl = (e & kGatherReflect) != 0;
+    const oaz_state st = samples[e & ~kGatherReflect].state;
     const int color = st.to_move & 1;
-    const uint32_t bit = sq_bit(sq);
+    const uint32_t bit = sq_bit(refl ? reflect_sq(sq) : sq);
     float* row = X0 + (size_t)(sq * B + b) * kInPad;
     float v[kInPad];
 #pragma unroll
@@ -86,7 +96,11 @@ __global__ void k_gather(const oaz_sample* samples, const int32_t* idx_all, cons
     v[1] = (st.kings[0] & bit) ? 1.0f : 0.0f;
     v[2] = (st.pawns[1] & bit) ? 1.0f : 0.0f;
     v[3] = (st.kings[1] & bit) ? 1.0f : 0.0f;
-    const int c0 = st.cards[color ? 2 : 0] & 15, c1 = st.cards[color ? 3 : 1] & 15;
+    int c0 = st.cards[color ? 2 : 0] & 15, c1 = st.cards[color ? 3 : 1] & 15;
+    if (refl) {
+        c0 = reflect_card(c0);
+        c1 = reflect_card(c1);
+    }
 #pragma unroll
     for (int c = 0; c < 16; ++c) v[4 + c] = (c == c0 || c == c1) ? 1.0f : 0.0f;
     v[20] = color == OAZ_BLUE ? 1.0f : 0.0f;
@@ -1180,12 +1194,27 @@ extern "C" int oaz_trainer_bind_device_samples(oaz_trainer* t, const oaz_sample*
 }
 
 extern "C" int oaz_trainer_set_batches(oaz_trainer* t, const int32_t* idx, int n_batches, int batch) {
+    return oaz_trainer_set_batches_reflect(t, idx, nullptr, n_batches, batch);
+}
+
+// The device copy of an entry is its index, with kGatherReflect set where its flag is: the step's pointers and
+// kernel arguments (and so the captured graph) are the same with and without flags.
+extern "C" int oaz_trainer_set_batches_reflect(oaz_trainer* t, const int32_t* idx, const uint8_t* reflect,
+                                               int n_batches, int batch) {
     if (!t || !idx || n_batches < 0 || batch < 16 || batch % 16 || batch > t->maxB)
         return oaz_set_err(OAZ_ERR_ARG, "trainer: batch must be a multiple of 16 in [16, %d]", t ? t->maxB : 0);
     const size_t n = (size_t)n_batches * batch;
     for (size_t i = 0; i < n; ++i)
         if (idx[i] < 0 || (size_t)idx[i] >= t->n_samples)
             return oaz_set_err(OAZ_ERR_ARG, "trainer: index %d out of range (%zu samples)", idx[i], t->n_samples);
+    std::vector<int32_t> flagged;
+    if (reflect) {
+        for (size_t i = 0; i < n; ++i)
+            if (reflect[i] > 1) return oaz_set_err(OAZ_ERR_ARG, "trainer: reflect flag %d of entry %zu is not 0 or 1", reflect[i], i);
+        flagged.resize(n);
+        for (size_t i = 0; i < n; ++i) flagged[i] = (int32_t)((uint32_t)idx[i] | (reflect[i] ? kGatherReflect : 0u));
+        idx = flagged.data();
+    }
     OAZ_ON_DEVICE(t->device);
     if (n > t->idx.size()) {
         HIP_TRY(hipStreamSynchronize(t->st));  // the old buffer is freed: after the work that reads it

@@ -8,7 +8,8 @@ from . import _abi
 from ._abi import OazError, load
 from .engine import Engine, SearchResult
 from .game import (CARD_NAMES, ORIGINAL_CARDS, Card, Deck, DoneMove, GameState, Move, MoveResult,
-                   PieceKind, PlayerColor, State)
+                   PieceKind, PlayerColor, State, reflect_card, reflect_moves, reflect_samples, reflect_square,
+                   reflect_states)
 from .mcts import (AlphaZeroMcts, AlphaZeroMctsConfig, ConvResNet, ConvResNetConfig, Options,
                    TrainingAlphaZeroMcts, reward)
 from .selfplay import SelfPlayData, TrainConfig, self_play
@@ -19,7 +20,7 @@ from .pure_mcts import Mcts, pure_mcts_search, pure_mcts_search_each
 from .alpha_beta import AlphaBeta, alpha_beta_generate_move, alpha_beta_search
 from .tournament import Tournament
 from .parameter_check import ParameterCheck
-from .trainer import Trainer, train_epochs
+from .trainer import Trainer, choose_batches_doubled, choose_reflect, train_epochs, train_epochs_dp
 from .train_loop import LoopConfig, Stats, train
 
 __all__ = [
@@ -30,4 +31,6 @@ __all__ = [
     "FightStatistics", "PitStatistics", "RandomAgent", "fight", "Mcts", "pure_mcts_search", "Trainer", "train_epochs",
     "LoopConfig", "Stats", "train", "AlphaBeta", "alpha_beta_search", "NativeRandomAgent", "native_fight",
     "alpha_beta_generate_move", "Tournament", "pure_mcts_search_each", "ParameterCheck",
+    "reflect_square", "reflect_card", "reflect_states", "reflect_moves", "reflect_samples", "choose_reflect",
+    "choose_batches_doubled", "train_epochs_dp",
 ]

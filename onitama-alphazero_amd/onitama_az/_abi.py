@@ -429,6 +429,12 @@ _PROTOS = {
     "oaz_trainer_train": (C.c_int, [_VOIDP, C.c_int, C.c_int]),
     "oaz_trainer_losses": (C.c_int, [_VOIDP, _P(C.c_double * 3)]),
     "oaz_trainer_sync": (C.c_int, [_VOIDP]),
+    "oaz_reflect_card": (C.c_int, [C.c_int]),
+    "oaz_reflect_states_host": (C.c_int, [_VOIDP, C.c_int, _VOIDP]),
+    "oaz_reflect_moves_host": (C.c_int, [_VOIDP, C.c_int, _VOIDP]),
+    "oaz_reflect_samples_host": (C.c_int, [_VOIDP, C.c_size_t, _VOIDP]),
+    "oaz_reflect_samples": (C.c_int, [_VOIDP, C.c_size_t, _VOIDP]),
+    "oaz_trainer_set_batches_reflect": (C.c_int, [_VOIDP, _VOIDP, _VOIDP, C.c_int, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

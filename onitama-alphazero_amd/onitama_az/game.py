@@ -95,11 +95,33 @@ def from_2d_to_1d(value: Tuple[int, int]) -> int:  # common/mod.rs:22-25
     return y * 5 + x
 
 
+def reflect_square(i: int) -> int:
+    """The left-right reflection (in the c-file) of square i; 25, the pass move's square, is fixed. The rules are
+    invariant under it when every card is replaced by `reflect_card` of it (include/onitama_az.h, "left-right
+    reflection"); the reference has no such thing (its `Card.mirror` is the 180-degree rotation Blue uses)."""
+    if not 0 <= i <= 25:
+        raise ValueError("a square is 0..24, or 25 for the pass move")
+    return i if i == 25 else 5 * (i // 5) + 4 - i % 5
+
+
+def reflect_card(card):
+    """The card whose moves are the left-right reflection of `card`'s: a Card for a Card, an index for an index
+    (oaz_reflect_card: Frog<->Rabbit, Goose<->Rooster, Horse<->Ox, Eel<->Cobra, the other eight fixed)."""
+    k = _abi.load().oaz_reflect_card(int(card.index if isinstance(card, Card) else card))
+    if k < 0:
+        raise ValueError("a card index is 0..15")
+    return ORIGINAL_CARDS[k] if isinstance(card, Card) else k
+
+
 @dataclass(frozen=True, order=True)
 class Move:  # move.rs:20-25 (field order = derive(Ord) order)
     from_: int
     to: int
     piece: PieceKind
+
+    def reflected(self) -> "Move":
+        """The move on the reflected board (reflect_square of both squares; the piece stays)."""
+        return Move(reflect_square(self.from_), reflect_square(self.to), self.piece)
 
     @staticmethod
     def from_2d(mov: Tuple[Tuple[int, int], Tuple[int, int]], piece: PieceKind) -> "Move":  # move.rs:107-122
@@ -136,6 +158,10 @@ class DoneMove:  # done_move.rs:3-7
 
     def is_pass(self) -> bool:
         return self.mov.from_ >= 25
+
+    def reflected(self) -> "DoneMove":
+        """The move on the reflected board; the card's deck slot stays (a reflected card keeps its slot)."""
+        return DoneMove(self.mov.reflected(), self.used_card_idx)
 
 
 class Deck:  # deck.rs:20-165
@@ -194,6 +220,12 @@ class State:  # state.rs:51-56
 
     def clone(self) -> "State":
         return State(self.deck.clone(), self.kings, self.pawns)
+
+    def reflected(self) -> "State":
+        """The left-right reflected position: every piece on reflect_square of its square, every card replaced
+        by reflect_card of it in the same deck slot (oaz_reflect_states_host)."""
+        st, _ = State.from_np(reflect_states(self.to_np(PlayerColor.Red))[0])
+        return st
 
     # -- marshalling --
     def to_c(self, color: PlayerColor) -> _abi.oaz_state:
@@ -318,6 +350,35 @@ def encode_batch(states: np.ndarray) -> np.ndarray:
     planes = np.zeros((len(states), 21, 5, 5), dtype=np.float32)
     _abi.check(_abi.load().oaz_encode(_abi.ptr(states), len(states), _abi.ptr(planes)))
     return planes
+
+
+def reflect_states(states: np.ndarray) -> np.ndarray:
+    """oaz_reflect_states_host over a STATE_DTYPE array (host only): the reflected positions, same shape."""
+    states = np.ascontiguousarray(states, dtype=_abi.STATE_DTYPE)
+    out = np.zeros_like(states)
+    _abi.check(_abi.load().oaz_reflect_states_host(_abi.ptr(states), states.size, _abi.ptr(out)))
+    return out
+
+
+def reflect_moves(moves: np.ndarray) -> np.ndarray:
+    """oaz_reflect_moves_host over a MOVE_DTYPE array (host only)."""
+    moves = np.ascontiguousarray(moves, dtype=_abi.MOVE_DTYPE)
+    out = np.zeros_like(moves)
+    _abi.check(_abi.load().oaz_reflect_moves_host(_abi.ptr(moves), moves.size, _abi.ptr(out)))
+    return out
+
+
+def reflect_samples(samples: np.ndarray, gpu: bool = False) -> np.ndarray:
+    """The reflected self-play records (state, pi, z) of a SAMPLE_DTYPE array: the state reflected, pi's entries
+    moved to the reflected `to` squares of the same hand slot, z kept. Bytes are moved, never recomputed, so twice
+    is the identity. Host only (oaz_reflect_samples_host); gpu=True runs the kernel instead (oaz_reflect_samples),
+    with the same result."""
+    samples = np.ascontiguousarray(samples, dtype=_abi.SAMPLE_DTYPE)
+    out = np.zeros_like(samples)
+    lib = _abi.load()
+    fn = lib.oaz_reflect_samples if gpu else lib.oaz_reflect_samples_host
+    _abi.check(fn(_abi.ptr(samples), samples.size, _abi.ptr(out)))
+    return out
 
 
 def initial_state_np(deck_idx: Sequence[int]) -> np.ndarray:

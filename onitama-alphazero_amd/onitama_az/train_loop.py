@@ -56,6 +56,10 @@ class LoopConfig:  # TrainConfig, train.rs:100-154 (defaults of Default::default
     # self-play temperature (oaz_config.temperature_plies): a game's first T plies draw the move in proportion to the
     # root visits; 0 = always the most visited move, as the reference (Q9). The pit and the arena never draw.
     temperature_plies: int = 0
+    # training on the left-right reflected records too (trainer.train_epochs `reflect`): 0 = off, as the reference;
+    # 1 = every drawn sample reflected with probability 1/2; 2 = the buffer together with its reflection (twice
+    # the steps per epoch). Self-play, the pit and the arena are not touched.
+    reflect_augment: int = 0
 
 
 @dataclass
@@ -129,10 +133,13 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
             # training epochs (train.rs:257-325)
             if world == 1:
                 hist = train_epochs(tr, samples, epochs=config.training_epochs, batch=config.train_batch_size,
-                                    seed=config.seed + 1000 + it)
+                                    seed=config.seed + 1000 + it, reflect=config.reflect_augment)
             else:
                 hist = train_epochs_dp(tr, samples, epochs=config.training_epochs, batch=config.train_batch_size,
-                                       seed=config.seed + 1000 + it, rank=rank, world=world, comm=comm)
+                                       seed=config.seed + 1000 + it, rank=rank, world=world, comm=comm,
+                                       reflect=config.reflect_augment)
+            if config.reflect_augment:  # the samples the epochs drew, reflected ones included
+                stats.games_played[-1]["positions_trained"] = sum(h.steps for h in hist) * config.train_batch_size
             k = max(1, len(hist))
             stats.iteration.append(it)
             stats.loss.append(sum(h.loss for h in hist) / k)

@@ -109,10 +109,19 @@ class Trainer:
         self._check(self._lib.oaz_trainer_bind_device_samples(self._h, C.c_void_p(dev_ptr), int(n)))
         self.n_samples = int(n)
 
-    def set_batches(self, idx: np.ndarray) -> None:
+    def set_batches(self, idx: np.ndarray, reflect: Optional[np.ndarray] = None) -> None:
+        """Upload the index matrix [n_batches, batch]. reflect (same shape, 0 / 1; None = all 0): a flagged entry
+        stands for the left-right reflected sample (oaz_trainer_set_batches_reflect): the step's gather produces its
+        planes, pi and z, with no copy of the buffer."""
         idx = np.ascontiguousarray(idx, dtype=np.int32)
         assert idx.ndim == 2
-        self._check(self._lib.oaz_trainer_set_batches(self._h, _abi.ptr(idx), idx.shape[0], idx.shape[1]))
+        if reflect is None:
+            self._check(self._lib.oaz_trainer_set_batches(self._h, _abi.ptr(idx), idx.shape[0], idx.shape[1]))
+            return
+        reflect = np.ascontiguousarray(reflect, dtype=np.uint8)
+        assert reflect.shape == idx.shape
+        self._check(self._lib.oaz_trainer_set_batches_reflect(self._h, _abi.ptr(idx), _abi.ptr(reflect), idx.shape[0],
+                                                              idx.shape[1]))
 
     # -- steps -------------------------------------------------------------------------------------
     def backward(self, b: int) -> None:
@@ -140,18 +149,66 @@ def choose_batches(rng: np.random.Generator, n_samples: int, batch: int, n_batch
     return np.stack([rng.choice(n_samples, size=batch, replace=False) for _ in range(n_batches)]).astype(np.int32)
 
 
+REFLECT_TAG = 0x5245464C  # "REFL": the reflect flags' generator is default_rng([REFLECT_TAG, seed])
+
+
+def choose_reflect(rng: np.random.Generator, shape) -> np.ndarray:
+    """Mode 1's flags: every entry 0 or 1 with probability 1/2 each (uint8, `shape`)."""
+    return rng.integers(0, 2, size=shape, dtype=np.uint8)
+
+
+def choose_batches_doubled(rng: np.random.Generator, n_samples: int, batch: int,
+                           n_batches: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Mode 2's draw: `choose_batches` over the 2 n virtual entries of the buffer together with its reflection,
+    entry j >= n being sample j - n reflected; returns (index matrix, flag matrix). The doubled buffer is never
+    made: no batch holds the same (sample, flag) pair twice, and may hold a sample and its reflection."""
+    virt = choose_batches(rng, 2 * n_samples, batch, n_batches)
+    return (virt % n_samples).astype(np.int32), (virt >= n_samples).astype(np.uint8)
+
+
+def epoch_batches(rng: np.random.Generator, flag_rng: np.random.Generator, n_samples: int, batch: int,
+                  reflect: int, rank: int = 0, world: int = 1) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """One epoch's (index matrix, flag matrix or None) for `reflect` (train_epochs). rng is the index generator and
+    flag_rng the flags' own: mode 0 and 1 draw from rng exactly what the loop without the feature draws. world > 1
+    (train_epochs_dp): every rank draws the whole matrices and gets its batch / world columns of both."""
+    if reflect not in (0, 1, 2):
+        raise ValueError("reflect is 0 (off), 1 (each entry with probability 1/2) or 2 (the doubled buffer)")
+    if reflect == 2:
+        idx, flags = choose_batches_doubled(rng, n_samples, batch, 2 * n_samples // batch)
+    else:
+        idx = choose_batches(rng, n_samples, batch, n_samples // batch)
+        flags = choose_reflect(flag_rng, idx.shape) if reflect == 1 else None
+    cols = slice(rank * (batch // world), (rank + 1) * (batch // world))
+    return idx[:, cols], (None if flags is None else flags[:, cols])
+
+
+def _set_batches(trainer, idx, flags) -> None:
+    if flags is None:
+        trainer.set_batches(idx)
+    else:
+        trainer.set_batches(idx, flags)
+
+
 def train_epochs(trainer: Trainer, samples: np.ndarray, epochs: int = 10, batch: int = 512,
-                 seed: int = 0) -> List[EpochLoss]:
+                 seed: int = 0, reflect: int = 0) -> List[EpochLoss]:
     """The epoch loop of train.rs:264-325 on one GPU (stops early, as the reference, when the
-    buffer holds fewer than `batch` samples)."""
+    buffer holds fewer than `batch` samples).
+
+    reflect: training on the left-right reflected records too (include/onitama_az.h, "left-right reflection"; the
+    reference does not). 0 = off: the index stream of a seed is what it always was. 1 = every drawn entry is
+    reflected with probability 1/2, the flags from a generator of their own (seed and REFLECT_TAG), the index
+    stream and the epoch length unchanged. 2 = the buffer together with its reflection: every batch a draw
+    without replacement from the 2 n entries, 2 n // batch batches per epoch."""
     rng = np.random.default_rng(seed)
+    flag_rng = np.random.default_rng([REFLECT_TAG, seed])
     trainer.load_samples(samples)
     out: List[EpochLoss] = []
     for _ in range(epochs):
         if len(samples) < batch:
             break
-        n = len(samples) // batch
-        trainer.set_batches(choose_batches(rng, len(samples), batch, n))
+        idx, flags = epoch_batches(rng, flag_rng, len(samples), batch, reflect)
+        n = len(idx)
+        _set_batches(trainer, idx, flags)
         trainer.train(0, n)
         v, p, k = trainer.losses()
         out.append(EpochLoss((v + p) / k, v / k, p / k, k))
@@ -181,14 +238,15 @@ def _allreduce_sum(t, comm, stream: int) -> None:
 
 
 def train_epochs_dp(trainer: Trainer, samples: np.ndarray, epochs: int, batch: int, seed: int, rank: int,
-                    world: int, comm=None) -> List[EpochLoss]:
+                    world: int, comm=None, reflect: int = 0) -> List[EpochLoss]:
     """Data-parallel epochs (train.rs:264-325 over `world` GPUs): the global batch `batch` is split
     into `world` shards of batch/world samples; the gradient buffer is summed over ranks (RCCL via
     `comm`, an onitama_az.dist.Comm) and applied with grad_scale 1/world, so every rank takes the
     same SGD step. All ranks draw the same index stream (same seed, same gathered `samples`) and take
     their shard. BN batch statistics are per shard (DDP without SyncBatchNorm); the running
     statistics are averaged over ranks after each epoch, and the reported losses are the global
-    ones, so every rank ends each epoch with identical weights and statistics."""
+    ones, so every rank ends each epoch with identical weights and statistics. reflect: as train_epochs; every
+    rank draws the same flags and takes the column slice of them that it takes of the indices."""
     import torch
     assert batch % world == 0 and (batch // world) % 16 == 0
     shard = batch // world
@@ -197,13 +255,13 @@ def train_epochs_dp(trainer: Trainer, samples: np.ndarray, epochs: int, batch: i
     # leave the all-reduce unordered against backward / apply)
     ts = torch.cuda.Stream()
     with torch.cuda.stream(ts):
-        out = _epochs_dp(trainer, samples, epochs, batch, seed, rank, world, comm, shard, ts.cuda_stream)
+        out = _epochs_dp(trainer, samples, epochs, batch, seed, rank, world, comm, shard, ts.cuda_stream, reflect)
     trainer.sync()
     trainer.set_stream(None)
     return out
 
 
-def _epochs_dp(trainer, samples, epochs, batch, seed, rank, world, comm, shard, stream) -> List[EpochLoss]:
+def _epochs_dp(trainer, samples, epochs, batch, seed, rank, world, comm, shard, stream, reflect=0) -> List[EpochLoss]:
     import torch
     trainer.set_stream(stream)
     dev = f"cuda:{torch.cuda.current_device()}"
@@ -212,14 +270,16 @@ def _epochs_dp(trainer, samples, epochs, batch, seed, rank, world, comm, shard, 
     nbn = int(trainer._lib.oaz_trainer_bn_stats_count(trainer.blocks))
     bn = torch.empty(nbn, dtype=torch.float32, device=dev)
     rng = np.random.default_rng(seed)
+    flag_rng = np.random.default_rng([REFLECT_TAG, seed])
     trainer.load_samples(samples)
     out: List[EpochLoss] = []
     for _ in range(epochs):
         if len(samples) < batch:
             break
-        nb = len(samples) // batch
-        idx = choose_batches(rng, len(samples), batch, nb)[:, rank * shard:(rank + 1) * shard]
-        trainer.set_batches(idx)
+        idx, flags = epoch_batches(rng, flag_rng, len(samples), batch, reflect, rank, world)
+        nb = len(idx)
+        assert idx.shape[1] == shard
+        _set_batches(trainer, idx, flags)
         for b in range(nb):
             trainer.backward(b)
             if world > 1:
