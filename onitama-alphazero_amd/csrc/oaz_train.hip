@@ -7,21 +7,32 @@
 // 16 rows of one square reads, for each on-board tap, the 16 contiguous rows of the neighbour
 // square, so off-board taps are skipped outright (169 of 225 (square, tap) pairs do work).
 //
-// Kernels per step (N residual blocks, L = 1 + 2N convs):
-//   gather                      samples[idx] -> X0 [R][32], pi [B][50], z [B]
-//   per conv: conv_fwd (MFMA 16x16x4 f32, + per-16-row BN partial sums) -> bn_act_cfin (every
-//          workgroup finalises the batch statistics from the partials, then applies BN + skip + ReLU)
-//   heads: head_conv (1x1, 3 channels) -> bn_fwd_fin x2 -> head_sample (value MLP, policy
-//          linear + softmax, loss, their backward, per-sample) -> head_bwd_fin -> head_bwd_rows
-//   per conv, last to first: bn_bwd_fin -> bn_bwd_apply -> wgrad (MFMA, per (tap, square)
-//          partials) -> wgrad_reduce -> conv_dgrad (the same conv kernel on flipped/transposed
-//          weights, epilogue = skip add + ReLU mask + BN-backward partial sums of the layer below)
-//   sgd (+ repack of the conv weights for the next step)
+// Kernels per step in launch order (N residual blocks, 1 + 2N convs; [2]: on the weight-gradient stream, beside
+// what follows on the step's own), one path, no run-time alternatives (-DOAZ_CONV_RG, -DOAZ_WSPLIT: A/B builds):
+//   gather:          k_gather        samples[idx] -> X0 [R][32], pi [B][50], z [B]
+//   tower_forward, per conv:
+//                    k_conv<FWD>     MFMA 16x16x4 f32, + BN partial sums per workgroup
+//                    k_bn_act_cfin   every workgroup finalises the batch statistics from the partials, then
+//                                    applies BN + skip + ReLU
+//   heads:           k_head_conv     1x1, 3 channels, + BN partial sums
+//                    k_bn_fwd_fin    both head BN layers in one launch
+//                    k_head_sample   value MLP, policy linear + softmax, loss, their backward, per sample
+//                    [2] k_loss_acc, k_colsum x2 (the heads' linear weight gradients)
+//                    k_bn_bwd_fin    both head BN layers
+//                    k_head_bwd_rows head BN + conv backward per trunk row, partials of the last trunk BN
+//                    [2] k_colsum x2 (the head convs' weight gradients)
+//   trunk_backward, per conv, last to first:
+//                    k_bn_bwd_fin -> k_bn_bwd_apply
+//                    [2] k_wgrad (MFMA 32x32x2 f32, per (tap, square, row split) partials) -> k_wgrad_reduce
+//                        -> k_colsum (the conv bias gradient)
+//                    k_conv<DGRAD>   not for the first conv: the same conv kernel on flipped/transposed weights,
+//                                    epilogue = skip add + ReLU mask + BN-backward partial sums of the layer below
+//   apply:           k_sgd           (+ the packed conv weights of the next step)
+// k_pack (set_weights) and k_bn_stats_io (data-parallel epoch end) are outside the step.
 // All reductions are two-stage with fixed order (deterministic; no float atomics).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
@@ -41,6 +52,9 @@ constexpr int kMaxConv = 1 + 2 * 16;
 constexpr int kHeadW = 64 * 25 + 64 + 64 + 1 + 2500 + 50;  // value MLP + policy linear grads
 constexpr int kHeadVW = 64 * 25 + 64 + 64 + 1;              // vh_linear1 w,b + vh_linear2 w,b
 constexpr int kHConvW = 64 + 1 + 128 + 2;                   // vh_conv w,b + policy_conv w,b
+constexpr int kHeadCh = 3;                // head BN channels: the value head's one, the policy head's two
+constexpr int kHeadStatN = (5 * kHeadCh + 3) / 4 * 4;  // hstat: mean, invstd, c1, mm, mx, in whole 16 bytes
+constexpr int kBnCoefN = 3 * kC;         // bcoef: c1, mm, mx
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -62,17 +76,17 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // ---- gather: create_tensor_from_state (common.rs:26-80) for samples[idx[b]] ----------------------
 // threads [0, R): one input row (square, sample); [R, R + 50B): pi; [R + 50B, R + 51B): z
-// bi: the batch number, or -1: the one kept on the device (*cur, advanced by the graph replay)
+// bi: the batch number
 // An index entry with bit 31 (kGatherReflect) set stands for the reflected sample (oaz_device.h "left-right
 // reflection", oaz_trainer_set_batches_reflect): its row of square sq is the sample's row of R(sq) with the two
 // hand cards replaced by their reflected cards, its pi[k][t] the sample's pi[k][R(t)], its z the sample's. The
 // samples are only read; without the bit every output is what it was.
 constexpr uint32_t kGatherReflect = 0x80000000u;
-__global__ void k_gather(const oaz_sample* samples, const int32_t* idx_all, const int32_t* cur, int bi, int B,
-                         float* X0, float* pi, float* z) {
+__global__ void k_gather(const oaz_sample* samples, const int32_t* idx_all, int bi, int B, float* X0, float* pi,
+                         float* z) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int R = B * 25;
-    const int32_t* idx = idx_all + (size_t)(bi >= 0 ? bi : *cur) * B;
+    const int32_t* idx = idx_all + (size_t)bi * B;
     if (t >= R) {
         const int u = t - R;
         if (u < B * 50) {
@@ -108,10 +122,6 @@ __global__ void k_gather(const oaz_sample* samples, const int32_t* idx_all, cons
     for (int c = 0; c < kInPad; c += 4) *reinterpret_cast<float4*>(row + c) = make_float4(v[c], v[c + 1], v[c + 2], v[c + 3]);
 }
 
-__global__ void k_set_batch(int32_t* cur, int v, int add) {
-    if (threadIdx.x == 0) *cur = add ? *cur + v : v;
-}
-
 // ---- 3x3 conv (forward, and dgrad on flipped weights) ------------------------------------------
 enum { CONV_FWD = 0, CONV_DGRAD = 1 };
 
@@ -134,6 +144,11 @@ struct ConvArgs {
 // channels. Per on-board tap the tap's packed weights (CH x 4 n-tiles x 64 lanes float4 = 16 KB
 // for 64 input channels) are staged once in LDS (double-buffered) and shared by the 4 waves;
 // each wave keeps 4 accumulators (one per 16-channel n-tile), so an A fragment feeds 4 MFMAs.
+#ifndef OAZ_CONV_RG
+#define OAZ_CONV_RG 2
+#endif
+constexpr int kConvRG = OAZ_CONV_RG;  // 16-row groups per conv workgroup (-DOAZ_CONV_RG=1 / 4: A/B variants)
+static_assert(kConvRG == 1 || kConvRG == 2 || kConvRG == 4, "OAZ_CONV_RG: 1, 2 or 4 row groups on 4 waves");
 template <int MODE, int CH, int RG>  // CH = input channels / 16; RG = 16-row groups per workgroup
 __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
     constexpr int NPW = RG;  // n-tiles per wave: 4 waves = RG row groups x (4 / RG) channel splits
@@ -257,12 +272,38 @@ __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
     }
 }
 
+// ---- the fixed-order sum of per-workgroup partials ----------------------------------------------------
+// part [nwg][2][pstride] (two sums per column), column coff + c: thread (c, q) of a 1024-thread workgroup adds
+// the rows w = q (mod 16) in double, four accumulators over rows 64 apart, the rest into the first, then the
+// pairwise fold. The callers add the 16 values of q in LDS. The forward and the backward statistics agree
+// because this order is stated once: the three finalisation kernels below call it.
+struct Sum2 {
+    double s1, s2;
+};
+__device__ __forceinline__ Sum2 part_sum2(const float* part, int nwg, int pstride, int coff, int c, int q) {
+    double a1[4] = {0.0, 0.0, 0.0, 0.0}, a2[4] = {0.0, 0.0, 0.0, 0.0};
+    int w = q;
+    for (; w + 48 < nwg; w += 64) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            a1[u] += part[(size_t)(w + 16 * u) * 2 * pstride + coff + c];
+            a2[u] += part[(size_t)(w + 16 * u) * 2 * pstride + pstride + coff + c];
+        }
+    }
+    for (; w < nwg; w += 16) {
+        a1[0] += part[(size_t)w * 2 * pstride + coff + c];
+        a2[0] += part[(size_t)w * 2 * pstride + pstride + coff + c];
+    }
+    return Sum2{(a1[0] + a1[1]) + (a1[2] + a1[3]), (a2[0] + a2[1]) + (a2[2] + a2[3])};
+}
+
 // ---- BN finalisation (forward): batch mean / biased var, running stats update ----------------------
 // part [nwg][2][pstride] (sum, sumsq) columns coff..coff+C-1; torch batch_norm(training=True):
 // y = (x - mean) * invstd * gamma + beta, invstd = 1/sqrt(var_biased + eps);
 // running = (1 - m) * running + m * {mean, var_unbiased}.
 // Channels c >= split take their running statistics from rmean2 / rvar2 [c - split] (the two heads' BN
 // layers in one launch: the value head's channel, then the policy head's two); split = C: one layer.
+// Its one use is the heads: the tower's layers are finalised by their consumer, k_bn_act_cfin.
 __global__ __launch_bounds__(1024) void k_bn_fwd_fin(const float* part, int nwg, int pstride, int coff, int C, double N,
                              float* rmean, float* rvar, float bn_mom, float eps, float* mean, float* invstd,
                              int split, float* rmean2, float* rvar2) {
@@ -270,21 +311,9 @@ __global__ __launch_bounds__(1024) void k_bn_fwd_fin(const float* part, int nwg,
     const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
     double s1 = 0.0, s2 = 0.0;
     if (c < C) {
-        double a1[4] = {0.0, 0.0, 0.0, 0.0}, a2[4] = {0.0, 0.0, 0.0, 0.0};
-        int w = q;
-        for (; w + 48 < nwg; w += 64) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a1[u] += part[(size_t)(w + 16 * u) * 2 * pstride + coff + c];
-                a2[u] += part[(size_t)(w + 16 * u) * 2 * pstride + pstride + coff + c];
-            }
-        }
-        for (; w < nwg; w += 16) {
-            a1[0] += part[(size_t)w * 2 * pstride + coff + c];
-            a2[0] += part[(size_t)w * 2 * pstride + pstride + coff + c];
-        }
-        s1 = (a1[0] + a1[1]) + (a1[2] + a1[3]);
-        s2 = (a2[0] + a2[1]) + (a2[2] + a2[3]);
+        const Sum2 s = part_sum2(part, nwg, pstride, coff, c, q);
+        s1 = s.s1;
+        s2 = s.s2;
     }
     sh[0][q][c] = s1;
     sh[1][q][c] = s2;
@@ -308,28 +337,9 @@ __global__ __launch_bounds__(1024) void k_bn_fwd_fin(const float* part, int nwg,
     }
 }
 
-// A = relu((Z - mean) * invstd * gamma + beta [+ skip])
-__global__ void k_bn_act(const float* Z, const float* mean, const float* invstd, const float* gamma,
-                         const float* beta, const float* skip, float* A, long long n) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t * 4 >= n) return;
-    const int c = (int)((t * 4) & 63);
-    const float4 z = reinterpret_cast<const float4*>(Z)[t];
-    float v[4] = {z.x, z.y, z.z, z.w};
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (skip) s = reinterpret_cast<const float4*>(skip)[t];
-    const float sk[4] = {s.x, s.y, s.z, s.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float y = (v[k] - mean[c + k]) * invstd[c + k] * gamma[c + k] + beta[c + k];
-        if (skip) y += sk[k];
-        v[k] = y > 0.0f ? y : 0.0f;
-    }
-    reinterpret_cast<float4*>(A)[t] = make_float4(v[0], v[1], v[2], v[3]);
-}
-
-// Consumer-side forward finalisation: k_bn_fwd_fin and k_bn_act in one launch (0.805 -> 0.762 ms per
-// batch-512 step). Every workgroup re-reduces the conv's [nwg][2][64] partials in its prologue (the same fixed
+// A = relu((Z - mean) * invstd * gamma + beta [+ skip]) with the forward finalisation on the consumer side: what
+// were a k_bn_fwd_fin launch and an apply launch in one (0.805 -> 0.762 ms per batch-512 step, DESIGN.md
+// section 8). Every workgroup re-reduces the conv's [nwg][2][64] partials in its prologue (the same fixed
 // order in every workgroup, so all of them apply the same statistics); workgroup 0 also writes the batch
 // mean / invstd for the backward pass and updates the running statistics.
 __global__ __launch_bounds__(1024) void k_bn_act_cfin(const float* part, int nwg, double N, float* rmean, float* rvar,
@@ -340,21 +350,9 @@ __global__ __launch_bounds__(1024) void k_bn_act_cfin(const float* part, int nwg
     __shared__ float cf[4][64];  // mean, invstd, gamma, beta
     const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
     {
-        double a1[4] = {0.0, 0.0, 0.0, 0.0}, a2[4] = {0.0, 0.0, 0.0, 0.0};
-        int w = q;
-        for (; w + 48 < nwg; w += 64) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a1[u] += part[(size_t)(w + 16 * u) * 128 + c];
-                a2[u] += part[(size_t)(w + 16 * u) * 128 + 64 + c];
-            }
-        }
-        for (; w < nwg; w += 16) {
-            a1[0] += part[(size_t)w * 128 + c];
-            a2[0] += part[(size_t)w * 128 + 64 + c];
-        }
-        sh[0][q][c] = (a1[0] + a1[1]) + (a1[2] + a1[3]);
-        sh[1][q][c] = (a2[0] + a2[1]) + (a2[2] + a2[3]);
+        const Sum2 s = part_sum2(part, nwg, 64, 0, c, q);
+        sh[0][q][c] = s.s1;
+        sh[1][q][c] = s.s2;
     }
     __syncthreads();
     if (q == 0) {
@@ -406,21 +404,9 @@ __global__ __launch_bounds__(1024) void k_bn_bwd_fin(const float* part, int nwg,
     const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
     double s1 = 0.0, s2 = 0.0;
     if (c < C) {
-        double a1[4] = {0.0, 0.0, 0.0, 0.0}, a2[4] = {0.0, 0.0, 0.0, 0.0};
-        int w = q;
-        for (; w + 48 < nwg; w += 64) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a1[u] += part[(size_t)(w + 16 * u) * 2 * pstride + coff + c];
-                a2[u] += part[(size_t)(w + 16 * u) * 2 * pstride + pstride + coff + c];
-            }
-        }
-        for (; w < nwg; w += 16) {
-            a1[0] += part[(size_t)w * 2 * pstride + coff + c];
-            a2[0] += part[(size_t)w * 2 * pstride + pstride + coff + c];
-        }
-        s1 = (a1[0] + a1[1]) + (a1[2] + a1[3]);
-        s2 = (a2[0] + a2[1]) + (a2[2] + a2[3]);
+        const Sum2 s = part_sum2(part, nwg, pstride, coff, c, q);
+        s1 = s.s1;
+        s2 = s.s2;
     }
     sh[0][q][c] = s1;
     sh[1][q][c] = s2;
@@ -618,11 +604,6 @@ __global__ __launch_bounds__(256) void k_head_conv(const float* A, const float* 
         part[(size_t)blockIdx.x * 8 + (j < 3 ? j : 4 + j - 3)] = s;  // [nwg][2][4]
     }
 }
-
-struct HeadStats {  // head BN batch statistics (channel 0 = value, 1..2 = policy)
-    float mean[3], invstd[3];
-    float c1[3], mm[3], mx[3];
-};
 
 // Value MLP (25 -> 64 -> 1, tanh), policy linear (50 -> 50) + softmax, alphaloss terms
 // (net.rs:234-243) and their backward down to the head BN outputs. One wave (64 lanes) per sample,
@@ -1001,17 +982,14 @@ struct oaz_trainer {
     wl::Layout L;  // the canonical blob (oaz_weights_layout.h): P, G and MOM are laid out by it
     HeadOff h{};   // its head offsets, as the kernels take them
     int nconv = 0, maxB = 0;
-    int cfin = -1;     // forward BN finalisation in k_bn_act_cfin (-1: one float4 per thread; A/B build: 0 = the
-                       // separate k_bn_fwd_fin + k_bn_act launches, n > 0 = n workgroups)
-    int conv_rg = 2;  // 16-row groups per conv workgroup (OAZ_CONV_RG=1|2|4 overrides; tuning knob)
     size_t nparam = 0;
     DevBuf<float> P, G, MOM;
     DevBuf<uint8_t> mask;
     DevBuf<float4> wf[kMaxConv], wd[kMaxConv];
     DevBuf<float> X0, Z[kMaxConv], A[kMaxConv], M[kMaxConv], DZ[2];
-    DevBuf<float> mean[kMaxConv], invstd[kMaxConv], bcoef;  // bcoef: c1, mm, mx [3][64]
+    DevBuf<float> mean[kMaxConv], invstd[kMaxConv], bcoef;  // bcoef: kBnCoefN floats, read through BnCoef
     DevBuf<float> part, bpart[2], wpart;
-    DevBuf<float> hz, g3, hstat;  // hstat: mean[3] invstd[3] c1[3] mm[3] mx[3]
+    DevBuf<float> hz, g3, hstat;  // hstat: kHeadStatN floats, read through HeadStat
     DevBuf<float> hpart, hwpart, hlpart, hcpart;
     DevBuf<float> pi, z;
     const oaz_sample* samples = nullptr;  // owned_samples, or the caller's (oaz_trainer_bind_device_samples)
@@ -1020,13 +998,7 @@ struct oaz_trainer {
     DevBuf<int32_t> idx;  // grow-only
     int n_batches = 0, batch = 0;
     DevBuf<double> loss_acc;
-    DevBuf<int32_t> cur;  // current batch number (device)
     Event ev_dz[2], ev_w[2], ev_h[2], ev_done;  // (after the buffers: destroyed before them)
-    // one captured SGD step (gather -> ... -> SGD -> batch+1), replayed by oaz_trainer_train
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    const void* graph_key[3] = {nullptr, nullptr, nullptr};
-    int graph_batch = 0;
 
     // `count` elements and a 16-byte pad, zero-filled on the trainer's stream: ordered before its work (create syncs)
     template <class T>
@@ -1034,10 +1006,6 @@ struct oaz_trainer {
         if (int rc = b.alloc(count + 16 / sizeof(T))) return rc;
         HIP_TRY(hipMemsetAsync(b, 0, b.size() * sizeof(T), own));
         return 0;
-    }
-    ~oaz_trainer() {  // what the members do not own
-        if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-        if (graph) (void)hipGraphDestroy(graph);
     }
 };
 
@@ -1074,14 +1042,14 @@ static int trainer_init(oaz_trainer* t) {
             return OAZ_ERR_HIP;
     }
     const size_t nwg_conv = R / 16;
-    if (t->alloc(t->X0, R * kInPad) || t->alloc(t->DZ[0], R * kC) || t->alloc(t->DZ[1], R * kC) || t->alloc(t->bcoef, 3 * 64) ||
+    if (t->alloc(t->X0, R * kInPad) || t->alloc(t->DZ[0], R * kC) || t->alloc(t->DZ[1], R * kC) || t->alloc(t->bcoef, kBnCoefN) ||
         t->alloc(t->part, nwg_conv * 128) || t->alloc(t->bpart[0], (R + 15) / 16 * 64) || t->alloc(t->bpart[1], (R + 15) / 16 * 64) ||
         t->alloc(t->wpart, (size_t)9 * 25 * kWSplit * 64 * 64) || t->alloc(t->hz, R * 4) || t->alloc(t->g3, R * 4) ||
-        t->alloc(t->hstat, 16) || t->alloc(t->hpart, ((R + 255) / 256 + (size_t)t->maxB / kHS + 1) * 8) ||
+        t->alloc(t->hstat, kHeadStatN) || t->alloc(t->hpart, ((R + 255) / 256 + (size_t)t->maxB / kHS + 1) * 8) ||
         t->alloc(t->hwpart, ((size_t)t->maxB / kHS + 1) * kHeadW) ||
         t->alloc(t->hlpart, ((size_t)t->maxB / kHS + 1) * 2) ||
         t->alloc(t->hcpart, ((R + 63) / 64) * (size_t)kHConvW) || t->alloc(t->pi, (size_t)t->maxB * 50) ||
-        t->alloc(t->z, (size_t)t->maxB) || t->alloc(t->loss_acc, 4) || t->alloc(t->cur, 1))
+        t->alloc(t->z, (size_t)t->maxB) || t->alloc(t->loss_acc, 4))
         return OAZ_ERR_HIP;
     const std::vector<uint8_t> mask = wl::sgd_mask(t->L);  // no SGD, no weight decay on the running statistics
     HIP_TRY(hipMemcpyAsync(t->mask, mask.data(), t->nparam, hipMemcpyHostToDevice, t->own));
@@ -1108,13 +1076,6 @@ extern "C" oaz_trainer* oaz_trainer_create(const oaz_train_config* cfg, int devi
     t->maxB = cfg->max_batch;
     t->L = wl::layout(cfg->blocks);
     t->h = head_off(t->L);
-#if OAZ_AB  // A/B build only: conv row-group override
-    if (const char* e = getenv("OAZ_CONV_RG")) {
-        const int v = atoi(e);
-        if (v == 1 || v == 2 || v == 4) t->conv_rg = v;
-    }
-    if (const char* e = getenv("OAZ_TRAIN_CFIN")) t->cfin = atoi(e) > 0 ? atoi(e) : 0;
-#endif
     t->nparam = t->L.total;
     if (trainer_init(t)) {  // the one failure exit: the partly built trainer goes, the error text stays
         oaz_trainer_destroy(t);
@@ -1198,7 +1159,7 @@ extern "C" int oaz_trainer_set_batches(oaz_trainer* t, const int32_t* idx, int n
 }
 
 // The device copy of an entry is its index, with kGatherReflect set where its flag is: the step's pointers and
-// kernel arguments (and so the captured graph) are the same with and without flags.
+// kernel arguments are the same with and without flags.
 extern "C" int oaz_trainer_set_batches_reflect(oaz_trainer* t, const int32_t* idx, const uint8_t* reflect,
                                                int n_batches, int batch) {
     if (!t || !idx || n_batches < 0 || batch < 16 || batch % 16 || batch > t->maxB)
@@ -1228,32 +1189,63 @@ extern "C" int oaz_trainer_set_batches_reflect(oaz_trainer* t, const int32_t* id
 }
 
 template <int MODE>
-static void launch_conv(int ch, int rg, dim3 grid, hipStream_t st, const ConvArgs& a) {
-#define OAZ_CONV(CHV, RGV) hipLaunchKernelGGL((k_conv<MODE, CHV, RGV>), grid, dim3(256), 0, st, a)
-    if (ch == 2) {
-        if (rg == 1) OAZ_CONV(2, 1); else if (rg == 2) OAZ_CONV(2, 2); else OAZ_CONV(2, 4);
-    } else {
-        if (rg == 1) OAZ_CONV(4, 1); else if (rg == 2) OAZ_CONV(4, 2); else OAZ_CONV(4, 4);
-    }
-#undef OAZ_CONV
+static void launch_conv(int ch, dim3 grid, hipStream_t st, const ConvArgs& a) {
+    if (ch == 2) hipLaunchKernelGGL((k_conv<MODE, 2, kConvRG>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_conv<MODE, 4, kConvRG>), grid, dim3(256), 0, st, a);
 }
 
-static int backward(oaz_trainer* t, int bi) {
-    const int B = t->batch, R = B * 25, NB = t->cfg.blocks, nl = t->nconv;
-    const wl::Layout& L = t->L;
-    const HeadOff& h = t->h;
-    hipStream_t st = t->st;
-    float* P = t->P;
-    float* G = t->G;
-    const float bn_mom = (float)t->cfg.bn_momentum, eps = (float)t->cfg.bn_eps;
-    const int rg = t->conv_rg, rows_wg = 16 * rg;
-    const int nwg_conv = 25 * ((B + rows_wg - 1) / rows_wg);
-    const dim3 conv_grid((B + rows_wg - 1) / rows_wg, 25);
-    hipLaunchKernelGGL(k_gather, dim3((R + 51 * B + 255) / 256), dim3(256), 0, st, t->samples, t->idx, t->cur, bi, B,
+// ---- one step: gather -> tower_forward -> heads -> trunk_backward, over one Step -------------------------
+struct HeadStat {  // hstat: the head BN layers' batch statistics and backward coefficients, kHeadCh floats each
+    float *mean, *invstd, *c1, *mm, *mx;
+};
+struct BnCoef {  // bcoef: the BN-backward coefficients of the trunk layer in hand, kC floats each
+    float *c1, *mm, *mx;
+};
+constexpr int kBwdU = 16;  // k_bn_bwd_apply rows per workgroup / 4 (4, 8, 32 measured slower)
+
+struct Step {
+    int B, R, nl;         // batch, rows (25 B), conv layers
+    hipStream_t st, st2;  // the critical path; the weight-gradient stream
+    dim3 conv_grid;
+    int nwg_conv, nwg_hc, nwg_hs, nwg_rows, nwg_bwd;  // workgroups (= rows of partials): conv, k_head_conv,
+                                                      // k_head_sample, k_head_bwd_rows, k_bn_bwd_apply
+    float *P, *G;
+    float bn_mom, eps;
+    HeadStat hs;
+    BnCoef bc;
+    float* hbpart;  // k_head_sample's BN partials, behind k_head_conv's in hpart
+};
+
+static Step make_step(oaz_trainer* t) {
+    Step s{};
+    s.B = t->batch, s.R = s.B * 25, s.nl = t->nconv;
+    s.st = t->st, s.st2 = t->st2;
+    constexpr int rows_wg = 16 * kConvRG;
+    s.conv_grid = dim3((s.B + rows_wg - 1) / rows_wg, 25);
+    s.nwg_conv = 25 * ((s.B + rows_wg - 1) / rows_wg);
+    s.nwg_hc = (s.R + 255) / 256;
+    s.nwg_hs = (s.B + kHS - 1) / kHS;
+    s.nwg_rows = (s.R + 63) / 64;
+    s.nwg_bwd = (s.R + 4 * kBwdU - 1) / (4 * kBwdU);
+    s.P = t->P, s.G = t->G;
+    s.bn_mom = (float)t->cfg.bn_momentum, s.eps = (float)t->cfg.bn_eps;
+    float* h = t->hstat;
+    s.hs = HeadStat{h, h + kHeadCh, h + 2 * kHeadCh, h + 3 * kHeadCh, h + 4 * kHeadCh};
+    float* c = t->bcoef;
+    s.bc = BnCoef{c, c + kC, c + 2 * kC};
+    s.hbpart = t->hpart + (size_t)s.nwg_hc * 8;
+    return s;
+}
+
+static void gather(oaz_trainer* t, const Step& s, int bi) {
+    hipLaunchKernelGGL(k_gather, dim3((s.R + 51 * s.B + 255) / 256), dim3(256), 0, s.st, t->samples, t->idx, bi, s.B,
                        t->X0, t->pi, t->z);
-    // ---- forward
-    for (int l = 0; l < nl; ++l) {
-        const wl::ConvBn& cv = L.tower[l];
+}
+
+static void tower_forward(oaz_trainer* t, const Step& s) {
+    float* P = s.P;
+    for (int l = 0; l < s.nl; ++l) {
+        const wl::ConvBn& cv = t->L.tower[l];
         ConvArgs a{};
         a.in = l == 0 ? t->X0 : t->A[l - 1];
         a.w = t->wf[l];
@@ -1261,98 +1253,92 @@ static int backward(oaz_trainer* t, int bi) {
         a.out = t->Z[l];
         a.part = t->part;
         a.chunks = l == 0 ? 2 : 4;
-        a.B = B;
-        launch_conv<CONV_FWD>(l == 0 ? 2 : 4, rg, conv_grid, st, a);
+        a.B = s.B;
+        launch_conv<CONV_FWD>(l == 0 ? 2 : 4, s.conv_grid, s.st, a);
         const float* skip = (l >= 2 && l % 2 == 0) ? t->A[l - 2] : nullptr;  // block output adds the block input
-        const long long n = (long long)R * kC;
-        if (t->cfin) {
-            const unsigned nwg_act = t->cfin > 0 ? (unsigned)t->cfin : (unsigned)((n / 4 + 1023) / 1024);
-            hipLaunchKernelGGL(k_bn_act_cfin, dim3(nwg_act), dim3(1024), 0, st, t->part, nwg_conv, (double)R,
-                               P + cv.mean, P + cv.var, bn_mom, eps, t->mean[l], t->invstd[l], t->Z[l],
-                               P + cv.gamma, P + cv.beta, skip, t->A[l], n);
-            continue;
-        }
-        hipLaunchKernelGGL(k_bn_fwd_fin, dim3(1), dim3(1024), 0, st, t->part, nwg_conv, 64, 0, 64, (double)R,
-                           P + cv.mean, P + cv.var, bn_mom, eps, t->mean[l], t->invstd[l], 64, nullptr, nullptr);
-        hipLaunchKernelGGL(k_bn_act, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, t->Z[l], t->mean[l],
-                           t->invstd[l], P + cv.gamma, P + cv.beta, skip, t->A[l], n);
+        const long long n = (long long)s.R * kC;
+        hipLaunchKernelGGL(k_bn_act_cfin, dim3((unsigned)((n / 4 + 1023) / 1024)), dim3(1024), 0, s.st, t->part,
+                           s.nwg_conv, (double)s.R, P + cv.mean, P + cv.var, s.bn_mom, s.eps, t->mean[l], t->invstd[l],
+                           t->Z[l], P + cv.gamma, P + cv.beta, skip, t->A[l], n);  // one float4 per thread
     }
-    (void)NB;
-    // ---- heads
+}
+
+// Leaves the BN-backward partials of the last trunk layer in t->part (nwg_rows rows) and its m in M[nl - 1].
+static int heads(oaz_trainer* t, const Step& s) {
+    const HeadOff& h = t->h;
+    const HeadStat& hs = s.hs;
+    float *P = s.P, *G = s.G;
+    hipStream_t st = s.st;
+    const int nl = s.nl, R = s.R;
     const float* AL = t->A[nl - 1];
-    const int nwg_hc = (R + 255) / 256;
-    hipLaunchKernelGGL(k_head_conv, dim3(nwg_hc), dim3(256), 0, st, AL, P, h, t->hz, t->hpart, R);
-    float* hmean = t->hstat;
-    float* hinv = t->hstat + 3;
-    float* hc1 = t->hstat + 6;
-    float* hmm = t->hstat + 9;
-    float* hmx = t->hstat + 12;
-    hipLaunchKernelGGL(k_bn_fwd_fin, dim3(1), dim3(1024), 0, st, t->hpart, nwg_hc, 4, 0, 3, (double)R,
-                       P + h.vrm, P + h.vrv, bn_mom, eps, hmean, hinv, 1, P + h.prm, P + h.prv);
-    const int nwg_hs = (B + kHS - 1) / kHS;
-    float* hbpart = t->hpart + (size_t)nwg_hc * 8;
-    hipLaunchKernelGGL(k_head_sample, dim3(nwg_hs), dim3(256), 0, st, t->hz, hmean, hinv, P, h, t->pi, t->z, B,
-                       t->cfg.value_loss_broadcast, t->g3, hbpart, t->hwpart, t->hlpart);
+    hipLaunchKernelGGL(k_head_conv, dim3(s.nwg_hc), dim3(256), 0, st, AL, P, h, t->hz, t->hpart, R);
+    hipLaunchKernelGGL(k_bn_fwd_fin, dim3(1), dim3(1024), 0, st, t->hpart, s.nwg_hc, 4, 0, kHeadCh, (double)R,
+                       P + h.vrm, P + h.vrv, s.bn_mom, s.eps, hs.mean, hs.invstd, 1, P + h.prm, P + h.prv);
+    hipLaunchKernelGGL(k_head_sample, dim3(s.nwg_hs), dim3(256), 0, st, t->hz, hs.mean, hs.invstd, P, h, t->pi, t->z,
+                       s.B, t->cfg.value_loss_broadcast, t->g3, s.hbpart, t->hwpart, t->hlpart);
     // the losses and the heads' weight gradients are off the critical path: the weight-gradient stream
     // sums them (st waits for st2 before SGD, and the next step's head_sample, ev_done)
     HIP_TRY(hipEventRecord(t->ev_h[0], st));
-    HIP_TRY(hipStreamWaitEvent(t->st2, t->ev_h[0], 0));
-    hipLaunchKernelGGL(k_loss_acc, dim3(1), dim3(64), 0, t->st2, t->hlpart, nwg_hs, t->loss_acc);
-    hipLaunchKernelGGL(k_colsum, dim3((kHeadVW + 63) / 64), dim3(1024), 0, t->st2, t->hwpart, nwg_hs, kHeadW, 0,
+    HIP_TRY(hipStreamWaitEvent(s.st2, t->ev_h[0], 0));
+    hipLaunchKernelGGL(k_loss_acc, dim3(1), dim3(64), 0, s.st2, t->hlpart, s.nwg_hs, t->loss_acc);
+    hipLaunchKernelGGL(k_colsum, dim3((kHeadVW + 63) / 64), dim3(1024), 0, s.st2, t->hwpart, s.nwg_hs, kHeadW, 0,
                        kHeadVW, G + h.l1w);
-    hipLaunchKernelGGL(k_colsum, dim3((2550 + 63) / 64), dim3(1024), 0, t->st2, t->hwpart, nwg_hs, kHeadW, kHeadVW,
+    hipLaunchKernelGGL(k_colsum, dim3((2550 + 63) / 64), dim3(1024), 0, s.st2, t->hwpart, s.nwg_hs, kHeadW, kHeadVW,
                        2550, G + h.plw);
-    hipLaunchKernelGGL(k_bn_bwd_fin, dim3(1), dim3(1024), 0, st, hbpart, nwg_hs, 4, 0, 3, (double)R, P + h.vg,
-                       hinv, G + h.vg, G + h.vb, hc1, hmm, hmx, 1, P + h.pg, G + h.pg, G + h.pb);
-    const int nwg_rows = (R + 63) / 64;
-    hipLaunchKernelGGL(k_head_bwd_rows, dim3(nwg_rows), dim3(256), 0, st, AL, t->Z[nl - 1], t->mean[nl - 1],
-                       t->invstd[nl - 1], t->hz, t->g3, hmean, hinv, hc1, hmm, hmx, P, h, t->M[nl - 1], t->part,
-                       t->hcpart, R);
+    hipLaunchKernelGGL(k_bn_bwd_fin, dim3(1), dim3(1024), 0, st, s.hbpart, s.nwg_hs, 4, 0, kHeadCh, (double)R,
+                       P + h.vg, hs.invstd, G + h.vg, G + h.vb, hs.c1, hs.mm, hs.mx, 1, P + h.pg, G + h.pg, G + h.pb);
+    hipLaunchKernelGGL(k_head_bwd_rows, dim3(s.nwg_rows), dim3(256), 0, st, AL, t->Z[nl - 1], t->mean[nl - 1],
+                       t->invstd[nl - 1], t->hz, t->g3, hs.mean, hs.invstd, hs.c1, hs.mm, hs.mx, P, h, t->M[nl - 1],
+                       t->part, t->hcpart, R);
     HIP_TRY(hipEventRecord(t->ev_h[1], st));
-    HIP_TRY(hipStreamWaitEvent(t->st2, t->ev_h[1], 0));
-    hipLaunchKernelGGL(k_colsum, dim3(2), dim3(1024), 0, t->st2, t->hcpart, nwg_rows, kHConvW, 0, 65, G + h.vcw);
-    hipLaunchKernelGGL(k_colsum, dim3(3), dim3(1024), 0, t->st2, t->hcpart, nwg_rows, kHConvW, 65, 130, G + h.pcw);
-    // ---- trunk backward; t->part holds the BN-backward partials of layer l (nwg, [2][64]).
-    // dZ of layer l feeds both dgrad(l) (on st, the critical path) and wgrad(l) (on st2); dZ and
-    // the bias partials are double-buffered so st never overwrites what st2 still reads.
-    int nwg_part = nwg_rows;
-    constexpr int kBwdU = 16;  // k_bn_bwd_apply rows per workgroup / 4 (4, 8, 32 measured slower)
-    const int nwg_bwd = (R + 4 * kBwdU - 1) / (4 * kBwdU);
+    HIP_TRY(hipStreamWaitEvent(s.st2, t->ev_h[1], 0));
+    hipLaunchKernelGGL(k_colsum, dim3(2), dim3(1024), 0, s.st2, t->hcpart, s.nwg_rows, kHConvW, 0, 65, G + h.vcw);
+    hipLaunchKernelGGL(k_colsum, dim3(3), dim3(1024), 0, s.st2, t->hcpart, s.nwg_rows, kHConvW, 65, 130, G + h.pcw);
+    return 0;
+}
+
+// The weight gradient of layer l (second stream): it needs dz(l) and the layer's input X only, and runs beside
+// dgrad(l) (started after dgrad(l) instead, beside the next layer's BN kernels: 0.846 vs 0.764 ms per step,
+// DESIGN §8)
+static int wgrad(oaz_trainer* t, const Step& s, int l, const float* dz) {
+    const int k = l & 1;
+    const wl::ConvBn& cv = t->L.tower[l];
+    HIP_TRY(hipEventRecord(t->ev_dz[k], s.st));
+    HIP_TRY(hipStreamWaitEvent(s.st2, t->ev_dz[k], 0));
+    const float* X = l == 0 ? t->X0 : t->A[l - 1];
+    if (l == 0)
+        hipLaunchKernelGGL(k_wgrad<1>, dim3(25, 9, kWSplit), dim3(256), 0, s.st2, dz, X, s.B, t->wpart);
+    else
+        hipLaunchKernelGGL(k_wgrad<2>, dim3(25, 9, kWSplit), dim3(256), 0, s.st2, dz, X, s.B, t->wpart);
+    const int cin = (int)cv.cin;
+    const int nred = 9 * kC * cin;
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3((nred + 255) / 256), dim3(256), 0, s.st2, t->wpart, l == 0 ? kInPad : kC,
+                       cin, s.G + cv.w);
+    hipLaunchKernelGGL(k_colsum, dim3(1), dim3(1024), 0, s.st2, t->bpart[k], s.nwg_bwd, 64, 0, 64, s.G + cv.b);
+    HIP_TRY(hipEventRecord(t->ev_w[k], s.st2));
+    return 0;
+}
+
+// t->part holds the BN-backward partials of layer l (nwg_part rows of [2][64]).
+// dZ of layer l feeds both dgrad(l) (on st, the critical path) and wgrad(l) (on st2); dZ and
+// the bias partials are double-buffered so st never overwrites what st2 still reads.
+static int trunk_backward(oaz_trainer* t, const Step& s) {
+    const BnCoef& bc = s.bc;
+    hipStream_t st = s.st;
+    int nwg_part = s.nwg_rows;
     bool used[2] = {false, false};
-    for (int l = nl - 1; l >= 0; --l) {
+    for (int l = s.nl - 1; l >= 0; --l) {
         const int k = l & 1;
-        const wl::ConvBn& cv = L.tower[l];
-        float* c1 = t->bcoef;
-        float* mm = t->bcoef + 64;
-        float* mx = t->bcoef + 128;
+        const wl::ConvBn& cv = t->L.tower[l];
         float* dz = t->DZ[k];
         if (used[k]) HIP_TRY(hipStreamWaitEvent(st, t->ev_w[k], 0));
-        hipLaunchKernelGGL(k_bn_bwd_fin, dim3(1), dim3(1024), 0, st, t->part, nwg_part, 64, 0, 64, (double)R,
-                           P + cv.gamma, t->invstd[l], G + cv.gamma, G + cv.beta, c1, mm, mx, 64, nullptr,
+        hipLaunchKernelGGL(k_bn_bwd_fin, dim3(1), dim3(1024), 0, st, t->part, nwg_part, 64, 0, 64, (double)s.R,
+                           s.P + cv.gamma, t->invstd[l], s.G + cv.gamma, s.G + cv.beta, bc.c1, bc.mm, bc.mx, 64, nullptr,
                            nullptr, nullptr);
-        hipLaunchKernelGGL(k_bn_bwd_apply<kBwdU>, dim3(nwg_bwd), dim3(256), 0, st, t->M[l], t->Z[l], t->mean[l],
-                           t->invstd[l], c1, mm, mx, dz, t->bpart[k], R);
-        // the weight gradient of layer l (second stream): it needs dz(l) and the layer's input X only, and runs
-        // beside dgrad(l) (started after dgrad(l) instead, beside the next layer's BN kernels: 0.846 vs 0.764 ms
-        // per step)
-        auto wgrad = [&]() -> int {
-            HIP_TRY(hipEventRecord(t->ev_dz[k], st));
-            HIP_TRY(hipStreamWaitEvent(t->st2, t->ev_dz[k], 0));
-            const float* X = l == 0 ? t->X0 : t->A[l - 1];
-            if (l == 0)
-                hipLaunchKernelGGL(k_wgrad<1>, dim3(25, 9, kWSplit), dim3(256), 0, t->st2, dz, X, B, t->wpart);
-            else
-                hipLaunchKernelGGL(k_wgrad<2>, dim3(25, 9, kWSplit), dim3(256), 0, t->st2, dz, X, B, t->wpart);
-            const int cin = (int)cv.cin;
-            const int nred = 9 * kC * cin;
-            hipLaunchKernelGGL(k_wgrad_reduce, dim3((nred + 255) / 256), dim3(256), 0, t->st2, t->wpart,
-                               l == 0 ? kInPad : kC, cin, G + cv.w);
-            hipLaunchKernelGGL(k_colsum, dim3(1), dim3(1024), 0, t->st2, t->bpart[k], nwg_bwd, 64, 0, 64, G + cv.b);
-            HIP_TRY(hipEventRecord(t->ev_w[k], t->st2));
-            used[k] = true;
-            return 0;
-        };
-        if (int rc = wgrad()) return rc;
+        hipLaunchKernelGGL(k_bn_bwd_apply<kBwdU>, dim3(s.nwg_bwd), dim3(256), 0, st, t->M[l], t->Z[l], t->mean[l],
+                           t->invstd[l], bc.c1, bc.mm, bc.mx, dz, t->bpart[k], s.R);
+        if (int rc = wgrad(t, s, l, dz)) return rc;
+        used[k] = true;
         if (l == 0) break;
         ConvArgs a{};
         a.in = dz;
@@ -1365,12 +1351,21 @@ static int backward(oaz_trainer* t, int bi) {
         a.invstd = t->invstd[l - 1];
         a.skip = (l % 2 == 1) ? t->M[l + 1] : nullptr;  // first conv of a block: add the block-output gradient
         a.chunks = 4;
-        a.B = B;
-        launch_conv<CONV_DGRAD>(4, rg, conv_grid, st, a);
-        nwg_part = nwg_conv;
+        a.B = s.B;
+        launch_conv<CONV_DGRAD>(4, s.conv_grid, st, a);
+        nwg_part = s.nwg_conv;
     }
-    HIP_TRY(hipEventRecord(t->ev_done, t->st2));
+    HIP_TRY(hipEventRecord(t->ev_done, s.st2));
     HIP_TRY(hipStreamWaitEvent(st, t->ev_done, 0));  // every gradient is in G before SGD / all-reduce
+    return 0;
+}
+
+static int backward(oaz_trainer* t, int bi) {
+    const Step s = make_step(t);
+    gather(t, s, bi);
+    tower_forward(t, s);
+    if (int rc = heads(t, s)) return rc;
+    if (int rc = trunk_backward(t, s)) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1468,58 +1463,16 @@ extern "C" int oaz_trainer_apply(oaz_trainer* t, float grad_scale) {
     return apply(t, grad_scale);
 }
 
-// One SGD step captured as a hipGraph (both streams; the batch number advances on the device),
-// rebuilt when the batch size, stream or buffers change. Opt-in (OAZ_TRAIN_GRAPH=1).
-static int ensure_graph(oaz_trainer* t) {
-    const void* key[3] = {t->samples, t->idx, t->st};
-    if (t->graph_exec && t->graph_batch == t->batch && !memcmp(key, t->graph_key, sizeof(key))) return 0;
-    if (t->graph_exec) (void)hipGraphExecDestroy(t->graph_exec);
-    if (t->graph) (void)hipGraphDestroy(t->graph);
-    t->graph_exec = nullptr;
-    t->graph = nullptr;
-    HIP_TRY(hipStreamBeginCapture(t->st, hipStreamCaptureModeThreadLocal));
-    int rc = backward(t, -1);
-    if (!rc) rc = apply(t, 1.0f);
-    if (!rc) hipLaunchKernelGGL(k_set_batch, dim3(1), dim3(64), 0, t->st, t->cur, 1, 1);
-    hipGraph_t g = nullptr;
-    const hipError_t e = hipStreamEndCapture(t->st, &g);
-    if (rc) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-    }
-    if (e != hipSuccess) return oaz_set_err(OAZ_ERR_HIP, "trainer: graph capture: %s", hipGetErrorString(e));
-    t->graph = g;
-    HIP_TRY(hipGraphInstantiate(&t->graph_exec, g, nullptr, nullptr, 0));
-    t->graph_batch = t->batch;
-    memcpy(t->graph_key, key, sizeof(key));
-    return 0;
-}
-
 extern "C" int oaz_trainer_train(oaz_trainer* t, int first, int count) {
     if (!t) return oaz_set_err(OAZ_ERR_ARG, "trainer: null");
     if (!t->samples || first < 0 || count < 0 || first + count > t->n_batches)
         return oaz_set_err(OAZ_ERR_STATE, "trainer: batches [%d, %d) not uploaded", first, first + count);
     OAZ_ON_DEVICE(t->device);
     if (count == 0) return 0;
-    // Plain stream launches by default: on this stack replaying the captured step (~65 kernels on
-    // two streams) measured slower (1.06 vs 0.87 ms at batch 512, 5 blocks); OAZ_TRAIN_GRAPH=1
-    // selects the graph path.
-#if OAZ_AB
-    const bool graph = getenv("OAZ_TRAIN_GRAPH") != nullptr;
-#else
-    const bool graph = false;
-#endif
-    if (!graph) {
-        for (int b = first; b < first + count; ++b) {
-            if (int rc = backward(t, b)) return rc;
-            if (int rc = apply(t, 1.0f)) return rc;
-        }
-        return 0;
+    for (int b = first; b < first + count; ++b) {
+        if (int rc = backward(t, b)) return rc;
+        if (int rc = apply(t, 1.0f)) return rc;
     }
-    if (int rc = ensure_graph(t)) return rc;
-    hipLaunchKernelGGL(k_set_batch, dim3(1), dim3(64), 0, t->st, t->cur, first, 0);
-    HIP_TRY(hipGetLastError());
-    for (int b = 0; b < count; ++b) HIP_TRY(hipGraphLaunch(t->graph_exec, t->st));
     return 0;
 }
 

@@ -55,3 +55,47 @@ def test_normalise_and_compare():
     assert compare(OLD, added) is not None and compare(added, OLD) is not None
     # a kernel added at the very end (one side a prefix of the other): different
     assert compare(OLD, OLD + _kernel("_ZN3oaz8k_selectENS_8TreeViewE", BODY)) is not None
+
+
+def _function(name, index, body=BODY):
+    """A function as the compiler prints it: its section, the "Begin function" line, labels numbered by the
+    function's place in the unit."""
+    return (f"\t.text\n\t.protected\t{name} ; -- Begin function {name}\n\t.globl\t{name}\n{name}:\n{body}"
+            f"\ts_cbranch_execz .LBB{index}_2\n.LBB{index}_2:{' ' * (12 - len(str(index)))}; in Loop: Header=BB{index}_2\n"
+            f"\ts_endpgm\n.Lfunc_end{index}:\n\t.size\t{name}, .Lfunc_end{index}-{name}\n")
+
+
+def _meta(name, nargs):
+    return "  - .args:\n" + "      - .offset: 0\n" * nargs + f"    .name:           {name}\n    .symbol:         {name}.kd\n"
+
+
+def _whole(functions):
+    """functions: [(symbol, body, kernel arguments)]"""
+    return ("\t.amdgcn_target \"amdgcn-amd-amdhsa--gfx950\"\n"
+            + "".join(_function(n, i, b) for i, (n, b, _) in enumerate(functions))
+            + "\t.text\n\t.p2alignl 6, 3212836864\n\t.amdgpu_metadata\n---\namdhsa.kernels:\n"
+            + "".join(_meta(n, k) for n, _, k in functions) + "amdhsa.target: x\n...\n\t.end_amdgpu_metadata\n")
+
+
+def test_per_function_report():
+    sys.path.insert(0, str(ROOT / "tools"))
+    from device_asm_diff import compare, compare_functions, function_key
+
+    assert function_key("_ZN2tr8k_gatherEPK10oaz_samplePKiS4_iiPfS5_S5_") == "tr::k_gather"
+    assert function_key("_ZN2tr6k_convILi1ELi4ELi2EEEvNS_8ConvArgsE") == "tr::k_conv<1,4,2>"
+    assert function_key("k_bn_stats_io") == "k_bn_stats_io"
+    old = _whole([("_ZN2tr8k_gatherEPKiS1_i", BODY, 3), ("_ZN2tr11k_set_batchEPiii", BODY, 3),
+                  ("_ZN2tr6k_convILi0ELi2ELi1EEEvNS_8ConvArgsE", BODY, 1),
+                  ("_ZN2tr6k_convILi0ELi2ELi2EEEvNS_8ConvArgsE", BODY, 1), ("_ZN2tr5k_sgdEPf", BODY, 1),
+                  ("_ZN2tr6k_packEPf", BODY, 1)])
+    # a kernel and a template instance gone (so every later function's labels are renumbered), one signature and
+    # one instruction changed, one argument layout changed under the same name, one kernel added
+    new = _whole([("_ZN2tr8k_gatherEPKii", BODY.replace("v_add", "v_sub"), 2),
+                  ("_ZN2tr6k_convILi0ELi2ELi2EEEvNS_8ConvArgsE", BODY, 1), ("_ZN2tr5k_sgdEPf", BODY, 2),
+                  ("_ZN2tr6k_packEPf", BODY, 1), ("_ZN2tr5k_newEPf", BODY, 1)])
+    assert compare(old, new) is not None
+    assert compare_functions(old, new) == [
+        ("tr::k_gather", "different"), ("tr::k_set_batch", "only in old"), ("tr::k_conv<0,2,1>", "only in old"),
+        ("tr::k_conv<0,2,2>", "identical"), ("tr::k_sgd", "different"), ("tr::k_pack", "identical"),
+        ("(rest of unit)", "identical"), ("tr::k_new", "only in new")]
+    assert all(v == "identical" for _, v in compare_functions(old, old))

@@ -6,6 +6,9 @@ differs between two compilations of the same code is taken out: the per-compilat
 the mangled names, which change with a template parameter or a type's name and shift the substitution
 indices inside other names, so each is replaced by its order of first appearance. The rest must be equal line
 for line. Exit status 0: all ten comparisons equal; 1: a difference, its first lines printed per file.
+--per-kernel splits a unit that differs at its function symbols and says of every kernel and device function
+whether it is identical, different, only in the old or only in the new build (a unit that loses a kernel reads
+"DIFFERENT" as a whole).
 The assembly is read only to compare two builds."""
 import argparse
 import concurrent.futures
@@ -19,6 +22,10 @@ from pathlib import Path
 
 UNITS = ("oaz_gpu.hip", "oaz_train.hip", "oaz_pure_mcts.hip", "oaz_alphabeta.hip", "oaz_arena.hip")
 MANGLED = re.compile(r"_Z[A-Za-z0-9_]+")
+# .LBB<function>_<block>, .Lfunc_end<function> and a comment's BB<function>_<block>: the function's number in the unit
+LOCAL = re.compile(r"\.L[A-Za-z_]+\d+(?:_\d+)?|\bBB\d+_\d+")
+BEGIN = re.compile(r"-- Begin function (\S+)")
+META_NAME = re.compile(r"    \.name:\s+(\S+)")
 
 
 def normalise(asm):
@@ -39,6 +46,66 @@ def compare(old_asm, new_asm, context=3):
     out = ["first difference at normalised line %d (%d lines old, %d new)" % (i + 1, len(a), len(b))]
     out += ["  old| " + s for s in a[i:i + context]] + ["  new| " + s for s in b[i:i + context]]
     return "\n".join(out)
+
+
+def split_functions(asm):
+    """{symbol: lines} of `asm`, one entry per function (kernel or device function): its text from the section
+    directive before its "-- Begin function" line to the next one's, and, for a kernel, its entry of the code
+    object's metadata (the argument layout). "(rest of unit)" is what belongs to no function: the head and the tail of the file."""
+    out, rest, cur, entry = {}, [], None, None
+    for line in asm.splitlines():
+        if "__hip_cuid_" in line:
+            continue
+        m = BEGIN.search(line)
+        if m or (cur is not None and line.startswith(("\t.p2alignl", "\t.amdgpu_metadata"))):  # (else: the tail)
+            prev = rest if cur is None else cur
+            cur = out.setdefault(m.group(1), []) if m else None
+            if prev and prev[-1].startswith(("\t.text", "\t.section")):  # the section directive of what follows
+                (rest if cur is None else cur).append(prev.pop())
+        if entry is not None and not line.startswith("    "):  # an entry of amdhsa.kernels ends: to its kernel
+            out.setdefault(next(m.group(1) for m in map(META_NAME.match, entry) if m), []).extend(entry)
+            entry = None
+        if cur is None and line.startswith("  - ."):
+            entry = []
+        (entry if entry is not None else rest if cur is None else cur).append(line)
+    out["(rest of unit)"] = rest
+    return out
+
+
+def function_key(sym):
+    """What names the same function in both builds: the qualified name without its parameter types (which a
+    changed signature changes), with the template arguments where they are integers: tr::k_conv<0,2,2>."""
+    m = re.match(r"_ZN?", sym)
+    if not m:
+        return sym
+    i, parts = m.end(), []
+    while sym[i:i + 1].isdigit():
+        n = re.match(r"\d+", sym[i:]).group(0)
+        parts.append(sym[i + len(n):i + len(n) + int(n)])
+        i += len(n) + int(n)
+    if not parts:
+        return sym
+    t = re.match(r"I((?:L[a-z]\d+E)+)E", sym[i:])
+    if t:
+        return "::".join(parts) + "<" + ",".join(re.findall(r"L[a-z](\d+)E", t.group(1))) + ">"
+    return "::".join(parts) + (" " + sym[i:] if sym[i:i + 1] == "I" else "")
+
+
+def normalise_function(lines):
+    """As normalise(), within one function: local labels are numbered by first appearance as well, and the
+    padding in front of a comment, which follows a label's length, is one blank."""
+    order = {}
+    number = lambda m: "@%d" % order.setdefault(m.group(0), len(order))
+    return [re.sub(r"\s+;", " ;", LOCAL.sub(number, MANGLED.sub(number, line))) for line in lines]
+
+
+def compare_functions(old_asm, new_asm):
+    """[(function, "identical" | "different" | "only in old" | "only in new")] in the old build's order, the
+    new build's own functions last."""
+    a = {function_key(k): normalise_function(v) for k, v in split_functions(old_asm).items()}
+    b = {function_key(k): normalise_function(v) for k, v in split_functions(new_asm).items()}
+    out = [(k, "only in old" if k not in b else "identical" if a[k] == b[k] else "different") for k in a]
+    return out + [(k, "only in new") for k in b if k not in a]
 
 
 def cxxflags(csrc, ab, extra):
@@ -65,6 +132,7 @@ def main():
     ap.add_argument("new_csrc")
     ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
     ap.add_argument("--extra", default="", help="the Makefile's EXTRA (-D tunables) for both trees")
+    ap.add_argument("--per-kernel", action="store_true", help="report every function of a unit that differs")
     ap.add_argument("-j", "--jobs", type=int, default=min(8, os.cpu_count() or 1))
     a = ap.parse_args()
     trees = {"old": os.path.abspath(a.old_csrc), "new": os.path.abspath(a.new_csrc)}
@@ -75,10 +143,13 @@ def main():
         bad = 0
         for ab in (0, 1):
             for unit in UNITS:
-                diff = compare(asm["old", unit, ab].result(), asm["new", unit, ab].result())
+                old, new = asm["old", unit, ab].result(), asm["new", unit, ab].result()
+                diff = compare(old, new)
                 print("%-20s -DOAZ_AB=%d  %s" % (unit, ab, "DIFFERENT" if diff else "identical"), flush=True)
                 if diff:
                     print(diff, flush=True)
+                    for name, verdict in compare_functions(old, new) if a.per_kernel else ():
+                        print("    %-14s %s" % (verdict, name), flush=True)
                     bad += 1
     print("%d of %d comparisons differ" % (bad, 2 * len(UNITS)))
     return 1 if bad else 0

@@ -1,6 +1,9 @@
 #!/bin/bash
 # Same-box A/B of training-step builds (bench.py --mode train, batch 512, 5 blocks): ROUNDS interleaved rounds
 # over onitama_az/libonitama_az_<name>.so for each name in $NAMES; test_train.py on each first (TESTS=1).
+# A -D variant library (the step reads no environment variable; OAZ_CONV_RG and OAZ_WSPLIT are build options), e.g.
+#   make -C onitama-alphazero_amd/csrc EXTRA=-DOAZ_CONV_RG=4 OUT=../onitama_az/libonitama_az_rg4.so OBJDIR=build_rg4
+# and a copy of another checkout's libonitama_az.so as libonitama_az_prev.so: NAMES="prev rg4" tools/train_ab.sh
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
 L=$PWD/onitama-alphazero_amd/onitama_az
 if [ -n "${TESTS:-}" ]; then
