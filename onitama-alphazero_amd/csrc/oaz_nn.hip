@@ -556,7 +556,7 @@ __device__ __forceinline__ float load(const char* img, int row, int c) { return 
 constexpr int8_t kSqOrderU[25] = {6, 7, 8, 11, 12, 13, 16, 17, 18, 0, 4, 20, 24, 2, 22,
                                   1, 3, 5, 10, 9, 14, 15, 19, 21, 23};
 // k_nn_h3's split: 17 / 8 in fp16x3 mode (GRP 7 / 8), 14 / 11 in bf16 mode (GRP 9 / 10). Same-box A/B
-// (tools/ab_libs.sh; profiles/r03_nn_split_ab.log, r03_nn_h1split_ab.log): fp16x3 16 / 9 within noise
+// (now tools/ab.py; profiles/r03_nn_split_ab.log, r03_nn_h1split_ab.log): fp16x3 16 / 9 within noise
 // of 17 / 8, 18 / 7 +1.2 %, 15 / 10 +0.2 %; bf16 6-block against 17 / 8: 16 / 9 -1.8 %, 15 / 10 -2.2 %,
 // 14 / 11 -3.0 %, 13 / 12 -2.4 % (its single product leaves the partner wave less to fill).
 #ifndef OAZ_H3_SPLIT

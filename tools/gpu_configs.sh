@@ -2,7 +2,7 @@
 # The other BASELINE configs through bench.py (C2, C5) and a 2-rank torchrun rehearsal of the
 # multi-GPU path on one GPU (gloo collectives, OAZ_BENCH_REHEARSE=1; its timings mean nothing).
 # Each step has its own time limit; stops at the first failure.
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 TAG=${TAG:-cfg}
 mkdir -p gpurun_out
 step() { local name=$1 out=$2; shift 2; echo "== $name"; "$@" > gpurun_out/$out.json 2> gpurun_out/$out.err; local rc=$?; echo "$name rc=$rc"; if [ $rc -ne 0 ]; then exit $rc; fi; }

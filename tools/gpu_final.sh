@@ -2,7 +2,7 @@
 # End-of-session check in one GPU call: parity suite + smoke (tools/gpu_tests.sh), the default bench
 # with its rocprofv3 trace (tools/gpu_profile.sh), then the other modes' lines. Each step has its own
 # time limit; the call stops at the first failure.
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 TAG=${TAG:-final}
 TAG=$TAG bash tools/gpu_tests.sh || exit $?
 TAG=$TAG bash tools/gpu_profile.sh || exit $?

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Full-size bench (its own PMC child passes included) + rocprofv3 kernel-trace stats of a short run
 # of the same workload. Each step has its own timeout; stops at the first failure.
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 TAG=${TAG:-prof}
 # both runs are --full ones: the side measurements in the line, the single-stream roofline leg at the end of the trace
 BENCH_ARGS="--full ${BENCH_ARGS:-}"; PROF_ARGS="--full ${PROF_ARGS:-}"

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU parity suite (one process), then smoke. Stops at the first failure/crash/timeout.
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${TAG:-gpu}
 timeout -k 10 1000 python -u -m pytest tests -x -v -m gpu --timeout 600 --timeout-method thread ${PYTEST_ARGS:-} > gpurun_out/pytest_$TAG.log 2>&1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Training-step bench (bench.py --mode train) + rocprofv3 kernel stats of the same command.
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 mkdir -p gpurun_out/prof_train
 PY=$(command -v python3)
 TRAIN_ARGS="--full ${TRAIN_ARGS:-}"  # with the PMC passes and the CPU baseline, as the line documents them

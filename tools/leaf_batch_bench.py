@@ -7,7 +7,8 @@ trained 3-block weights (tests/golden/weights_3block_trained.npy). Two batch siz
 and `--positions` seeded mid-game positions, each searched alone: "ms per move" is one oaz_search of one root) and
 64 roots (64 seeded positions in one oaz_search: ms per move = that call), at 400 and 5 000 playouts, for
 L in 0 (k_search_lat), 1, 2, 4, 8, 16 (k_search_par). Every (batch, playouts) pair runs in a child process of its
-own under `timeout`, one at a time; a child that is killed, aborts or faults ends the whole run.
+own under `timeout`, one at a time; the first child without exit status 0 and a result ends the whole run
+(tools/ab.py).
 
 Per configuration: one untimed search of every root set (code objects, first touches), then `--reps` timed
 searches of each, the host's monotonic clock around oaz_search (upload + one launch + finalize + the copies back,
@@ -34,13 +35,13 @@ import datetime
 import json
 import math
 import statistics
-import subprocess
 import sys
 import time
 from pathlib import Path
 
+import ab
+
 ROOT = Path(__file__).resolve().parents[1]
-FAULTS = {124, 134, 137, 139}  # time limit, abort, kill, segmentation fault: nothing more is started on the GPU
 WEIGHTS = ROOT / "tests" / "golden" / "weights_3block_trained.npy"
 C_PUCT = math.sqrt(2.0)
 
@@ -142,16 +143,6 @@ def fight_child(args) -> None:
         "caveat": "the small, briefly trained 3-block golden network; sides alternate, a deck dealt per game"}), flush=True)
 
 
-def run_child(extra, limit):
-    """A child process under `timeout`; (its RESULT lines as dicts, exit status)."""
-    cmd = ["timeout", "-k", "10", str(limit), sys.executable, str(Path(__file__).resolve())] + extra
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    res = [json.loads(ln[7:]) for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-    if not res or p.returncode:
-        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-    return res, p.returncode
-
-
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None)
@@ -181,19 +172,16 @@ def main() -> None:
            "network": "3 blocks, tests/golden/weights_3block_trained.npy, fp16x3 split, c = sqrt 2",
            "runs": [], "parent_runs": [], "fight": None}
 
-    def save():
-        out.parent.mkdir(parents=True, exist_ok=True)
-        out.write_text(json.dumps(doc, indent=1) + "\n")
-
+    run, me = ab.Run(out, doc), [sys.executable, str(Path(__file__).resolve())]
     for batch in [int(x) for x in args.batches.split(",")]:
         for sims in [int(x) for x in args.playouts.split(",")]:
-            order = [(None, "runs", args.ls)]
+            sides = [(None, "runs", args.ls)]
             if args.parent:  # this tree and the parent, alternating, twice each
-                order = [(None, "runs", args.ls), (Path(args.parent) / "onitama-alphazero_amd", "parent_runs", "0")] * 2
-            for k, (pkg, key, ls) in enumerate(order):
+                sides.append((Path(args.parent) / "onitama-alphazero_amd", "parent_runs", "0"))
+            for k, (pkg, key, ls) in enumerate(ab.schedule(sides, 2 if args.parent else 1)):
                 extra = ["--child", "--batch", str(batch), "--sims", str(sims), "--ls", ls, "--reps", str(args.reps),
                          "--positions", str(args.positions)] + (["--pkg", str(pkg)] if pkg else [])
-                res, rc = run_child(extra, 600)
+                res = run.child(f"{'parent' if pkg else 'this tree'} roots {batch} playouts {sims}", me + extra, 600)
                 for r in res:
                     r["run"] = k // 2
                     doc[key].append(r)
@@ -201,17 +189,11 @@ def main() -> None:
                           f"{r['ms_per_move_median']:8.3f} ms ({r['ms_per_move_min']:.3f} .. {r['ms_per_move_max']:.3f})"
                           + (f"  rounds {r['rounds_per_search']:.1f} discarded {r['discarded_walks_per_search']:.2f}"
                              if r["leaf_batch"] else ""), flush=True)
-                save()
-                if rc in FAULTS or rc < 0 or rc != 0 or not res:
-                    raise SystemExit(f"the child ended with status {rc}: nothing more is started")
+                run.save()
     if args.fight > 0:
-        res, rc = run_child(["--fight-child", "--fight", str(args.fight), "--sims", "400"], 900)
-        doc["fight"] = res[0] if res else None
-        print(f"fight: rc {rc} {doc['fight']}", flush=True)
-        save()
-        if rc != 0 or not res:
-            raise SystemExit(f"the fight ended with status {rc}")
-    save()
+        doc["fight"] = run.child("fight", me + ["--fight-child", "--fight", str(args.fight), "--sims", "400"], 900)[0]
+        print(f"fight: {doc['fight']}", flush=True)
+    run.save()
     print(f"wrote {out}")
 
 

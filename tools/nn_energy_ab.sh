@@ -3,7 +3,7 @@
 # (rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace: cycles / duration) of the A/B build's ablations
 # (timing only, wrong results): 0 product body, 40 no conv A reads, 41 no conv B loads, 47 conv B loads
 # of one step (L1 hits instead of L2), 49 conv A reads performed but discarded (stale MFMA operands).
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 export OAZ_LIB=$PWD/onitama-alphazero_amd/onitama_az/libonitama_az_ab.so
 OUT=gpurun_out/energy; mkdir -p $OUT
 PY=$(command -v python3)

@@ -3,7 +3,7 @@
 # launched back to back on one engine (tools/nn_prof.py: 65 536 positions per launch, host copies between
 # launches, no tree kernels) against the same kernel inside the C3 self-play loop (bench.py's PMC passes:
 # the two game parts' tree kernels and the root-noise kernel run between its launches).
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/nn_l2}; mkdir -p $OUT
 PY=$(command -v python3)
 i=0

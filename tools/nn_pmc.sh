@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ counter passes over the NN kernel (tools/nn_prof.py), one rocprofv3 run per pass, each under its
 # own timeout; summary per counter (per-dispatch mean over the k_nn_ dispatches) in gpurun_out/pmc/summary.txt.
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/pmc}; mkdir -p $OUT
 PY=$(command -v python3)
 i=0

@@ -4,8 +4,9 @@ flags cost per SGD step, and how far a network is from reflection symmetry with 
 tool; bench.py is the flagship's and is not touched. What the augmentation is worth in playing strength is not
 measured here.
 
-Every measurement runs in a child process of its own under `timeout`, one at a time; a child that is killed,
-aborts or faults ends the whole run. One child first plays the data: a training buffer (`--games` self-play games,
+Every measurement runs in a child process of its own under `timeout`, one at a time; the first child
+without exit status 0 and a result ends the whole run (tools/ab.py). One child first plays the data: a training
+buffer (`--games` self-play games,
 3-block random-init network seed 0, `--sims` simulations, root noise) and, from another seed, the fixed positions
 the gaps are measured on (the first `--positions` records of as many games).
 
@@ -32,14 +33,14 @@ import argparse
 import datetime
 import json
 import statistics
-import subprocess
 import sys
 import tempfile
 import time
 from pathlib import Path
 
+import ab
+
 ROOT = Path(__file__).resolve().parents[1]
-FAULTS = {124, 134, 137, 139}  # time limit, abort, kill, segmentation fault: nothing more is started on the GPU
 BATCH, STEP_BLOCKS, NET_BLOCKS = 512, 5, 3
 
 
@@ -149,31 +150,12 @@ def child_gap(args) -> None:
                                   "networks": out}), flush=True)
 
 
-def run_child(args, mode, data, case=None, pkg=None, limit=600):
-    """One measurement in a child process under `timeout`; (result dict or None, exit status)."""
+def child_cmd(args, mode, data, case=None, pkg=None) -> list:
+    """The command of one measurement's child process."""
     cmd = [sys.executable, str(Path(__file__).resolve()), "--child", mode, "--data", data, "--games", str(args.games),
            "--sims", str(args.sims), "--positions", str(args.positions), "--batches", str(args.batches),
            "--reps", str(args.reps), "--epochs", str(args.epochs), "--passes", str(args.passes)]
-    if case:
-        cmd += ["--case", case]
-    if pkg:
-        cmd += ["--pkg", str(pkg)]
-    p = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, capture_output=True, text=True)
-    res = None
-    for ln in p.stdout.splitlines():
-        if ln.startswith("RESULT "):
-            res = json.loads(ln[7:])
-    if res is None:
-        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-    return res, p.returncode
-
-
-def absent_verdict(mine, parent):
-    """"flags absent" against the parent, in ms per step: the slower of this tree's runs, the slower of the
-    parent's, the parent's spread."""
-    a, b = sorted(r["median_ms_per_step"] for r in mine), sorted(r["median_ms_per_step"] for r in parent)
-    return {"this_tree_median_ms_per_step": a, "parent_median_ms_per_step": b, "parent_spread_ms": b[-1] - b[0],
-            "this_tree_slower_by_ms": a[-1] - b[-1], "accepted": (a[-1] - b[-1]) <= (b[-1] - b[0])}
+    return cmd + (["--case", case] if case else []) + (["--pkg", str(pkg)] if pkg else [])
 
 
 def main() -> None:
@@ -204,34 +186,35 @@ def main() -> None:
            "out_of_scope": "what the augmentation is worth in playing strength",
            "data": None, "step_time": [], "step_time_parent": [], "absent_against_parent": None, "reflection_gap": None}
 
-    def save():
-        out.parent.mkdir(parents=True, exist_ok=True)
-        out.write_text(json.dumps(doc, indent=1) + "\n")
+    run = ab.Run(out, doc)
 
     def one(mode, data, case=None, pkg=None):
-        res, rc = run_child(args, mode, data, case=case, pkg=pkg)
-        print(f"{mode} {case or ''} {'parent' if pkg else 'this tree'}: rc {rc} "
-              f"{res and res.get('median_ms_per_step', '')}", flush=True)
-        if rc in FAULTS or rc < 0 or res is None:
-            save()
-            raise SystemExit(f"the child ended with status {rc}: nothing more is started")
+        what = f"{mode} {case or ''} {'parent' if pkg else 'this tree'}"
+        res = run.child(what, child_cmd(args, mode, data, case=case, pkg=pkg), 600)[-1]
+        print(f"{what}: {res.get('median_ms_per_step', '')}", flush=True)
         return res
 
     with tempfile.TemporaryDirectory() as tmp:
         data = str(Path(tmp) / "reflect")
         doc["data"] = one("data", data)
-        save()
-        parent = Path(args.parent) / "onitama-alphazero_amd" if args.parent else None
-        for pkg, key in ([(None, "step_time"), (parent, "step_time_parent")] * 2 if parent else [(None, "step_time")] * 2):
+        run.save()
+        sides = [(None, "step_time")]
+        if args.parent:  # this tree and the parent, alternating
+            sides.append((Path(args.parent) / "onitama-alphazero_amd", "step_time_parent"))
+        for pkg, key in ab.schedule(sides, 2):
             doc[key].append(one("step", data, case="absent", pkg=pkg))
-            save()
-        if parent:
-            doc["absent_against_parent"] = absent_verdict(doc["step_time"], doc["step_time_parent"])
+            run.save()
+        if args.parent:  # "flags absent" against the parent, in ms per step
+            mine, theirs = ([r["median_ms_per_step"] for r in doc[k]] for k in ("step_time", "step_time_parent"))
+            v = ab.spread_verdict(mine, theirs, higher_is_better=False)
+            doc["absent_against_parent"] = {
+                "this_tree_median_ms_per_step": v["mine"], "parent_median_ms_per_step": v["other"],
+                "parent_spread_ms": v["other_spread"], "this_tree_slower_by_ms": v["behind_by"], "accepted": v["accepted"]}
         for case in ("random", "all"):
             doc["step_time"].append(one("step", data, case=case))
-            save()
+            run.save()
         doc["reflection_gap"] = one("gap", data)
-    save()
+    run.save()
     print(f"wrote {out}")
 
 

@@ -1,8 +1,10 @@
 import sys, numpy as np
-sys.path.insert(0, '/root/repo/onitama-alphazero_amd'); sys.path.insert(0, '/root/repo/tests')
+from pathlib import Path
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / 'onitama-alphazero_amd')); sys.path.insert(0, str(ROOT / 'tests'))
 import oracle_ffi as orc
 from onitama_az.weights import named_from_blob, random_weights
-d = np.load('/root/repo/tests/golden/nn_golden.npz')
+d = np.load(ROOT / 'tests/golden/nn_golden.npz')
 states = d['states']
 planes = np.stack([orc.encode(s) for s in states]).astype(np.float64)  # [B,21,5,5]
 
@@ -71,7 +73,7 @@ def forward(t, blocks, mode, stats=None):
     z = np.exp(z - z.max(1, keepdims=True)); p = z / z.sum(1, keepdims=True)
     return p, v
 
-for name, blob, blocks in (('trained3', np.load('/root/repo/tests/golden/weights_3block_trained.npy'), 3), ('random3', random_weights(0, 3), 3), ('random6', random_weights(1, 6), 6)):
+for name, blob, blocks in (('trained3', np.load(ROOT / 'tests/golden/weights_3block_trained.npy'), 3), ('random3', random_weights(0, 3), 3), ('random6', random_weights(1, 6), 6)):
     t = named_from_blob(blob, blocks)
     st = []
     p64, v64 = forward(t, blocks, 'f64', st)
@@ -89,7 +91,7 @@ def split_rtz(x):
     x = x.astype(np.float32); h = rtz16(x); l = rtz16((x - h).astype(np.float32)); return h, l
 split_f16x2 = split_rtz
 print('--- RTZ split')
-for name, blob, blocks in (('trained3', np.load('/root/repo/tests/golden/weights_3block_trained.npy'), 3), ('random6', random_weights(1, 6), 6)):
+for name, blob, blocks in (('trained3', np.load(ROOT / 'tests/golden/weights_3block_trained.npy'), 3), ('random6', random_weights(1, 6), 6)):
     t = named_from_blob(blob, blocks)
     p64, v64 = forward(t, blocks, 'f64')
     p, v = forward(t, blocks, 'h3')

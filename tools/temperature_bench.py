@@ -5,7 +5,7 @@ touched.
 
 The flagship's engine (3-block network, random-init weights seed 0, fp16x3 split, 400 simulations, root noise,
 fixed deck, compact 0, automatic parts). Every configuration runs in a child process of its own under `timeout`,
-one at a time; a child that is killed, aborts or faults ends the whole run.
+one at a time; the first child without exit status 0 and a result ends the whole run (tools/ab.py).
 
 Throughput (`--sizes`, default 4 096 and 65 536 games; T in `--temps`, default 0, 8, 30): staggered starts,
 `--warmup` plies, then `--reps` timed windows of `--plies` plies each, the host's monotonic clock around
@@ -30,13 +30,13 @@ import argparse
 import datetime
 import json
 import statistics
-import subprocess
 import sys
 import time
 from pathlib import Path
 
+import ab
+
 ROOT = Path(__file__).resolve().parents[1]
-FAULTS = {124, 134, 137, 139}  # time limit, abort, kill, segmentation fault: nothing more is started on the GPU
 
 
 def engine_kw(_abi, args, **more):
@@ -112,27 +112,11 @@ def child_diversity(args) -> None:
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def run_child(args, mode, games, T, pkg=None, limit=900):
-    """The configuration in a child process under `timeout`; (result dict or None, exit status)."""
+def child_cmd(args, mode, games, T, pkg=None) -> list:
+    """The command of one configuration's child process."""
     cmd = [sys.executable, str(Path(__file__).resolve()), "--child", mode, "--games", str(games), "--temperature", str(T),
            "--sims", str(args.sims), "--warmup", str(args.warmup), "--plies", str(args.plies), "--reps", str(args.reps)]
-    if pkg:
-        cmd += ["--pkg", str(pkg)]
-    p = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, capture_output=True, text=True)
-    res = None
-    for ln in p.stdout.splitlines():
-        if ln.startswith("RESULT "):
-            res = json.loads(ln[7:])
-    if res is None:
-        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-    return res, p.returncode
-
-
-def off_verdict(mine, parent):
-    """T = 0 against the parent: the slower of this tree's runs, the slower of the parent's, the parent's spread."""
-    a, b = sorted(r["median_plies_per_s"] for r in mine), sorted(r["median_plies_per_s"] for r in parent)
-    return {"this_tree_median_plies_per_s": a, "parent_median_plies_per_s": b, "parent_spread": b[-1] - b[0],
-            "this_tree_slower_by": b[0] - a[0], "accepted": (b[0] - a[0]) <= (b[-1] - b[0])}
+    return cmd + (["--pkg", str(pkg)] if pkg else [])
 
 
 def main() -> None:
@@ -163,37 +147,34 @@ def main() -> None:
                      "window. diversity: selfplay_run of games 0 .. n-1 on n slots, all records fetched",
            "runs": [], "parent_runs": [], "off_against_parent": {}, "diversity": []}
 
-    def save():
-        out.parent.mkdir(parents=True, exist_ok=True)
-        out.write_text(json.dumps(doc, indent=1) + "\n")
+    run = ab.Run(out, doc)
 
     def one(mode, games, T, pkg, key):
-        res, rc = run_child(args, mode, games, T, pkg=pkg)
-        what = res and (round(res["median_plies_per_s"], 1) if mode == "throughput" else res["distinct_games"])
-        print(f"{mode} games {games} T {T} {'parent' if pkg else 'this tree'}: rc {rc} {what}", flush=True)
-        if res:
-            doc[key].append(res)
-        save()
-        if rc in FAULTS or rc < 0 or res is None:
-            raise SystemExit(f"the child ended with status {rc}: nothing more is started")
+        what = f"{mode} games {games} T {T} {'parent' if pkg else 'this tree'}"
+        res = run.child(what, child_cmd(args, mode, games, T, pkg=pkg), 900)[-1]
+        print(f"{what}: {round(res['median_plies_per_s'], 1) if mode == 'throughput' else res['distinct_games']}", flush=True)
+        doc[key].append(res)
+        run.save()
 
     for games in ([] if args.no_throughput else [int(x) for x in args.sizes.split(",")]):
         for T in temps:
-            order = [(None, "runs")]
-            if T == 0:  # twice; with --parent this tree and the parent, alternating
-                order = [(None, "runs"), (Path(args.parent) / "onitama-alphazero_amd", "parent_runs")] * 2 if args.parent \
-                    else [(None, "runs")] * 2
-            for pkg, key in order:
+            sides = [(None, "runs")]
+            if T == 0 and args.parent:  # this tree and the parent, alternating
+                sides.append((Path(args.parent) / "onitama-alphazero_amd", "parent_runs"))
+            for pkg, key in ab.schedule(sides, 2 if T == 0 else 1):
                 one("throughput", games, T, pkg, key)
-        if args.parent and 0 in temps:
-            doc["off_against_parent"][str(games)] = off_verdict(
-                [r for r in doc["runs"] if r["games"] == games and r["temperature_plies"] == 0],
-                [r for r in doc["parent_runs"] if r["games"] == games])
-            save()
+        if args.parent and 0 in temps:  # T = 0 against the parent, in plies/s
+            off = [r["median_plies_per_s"] for r in doc["runs"] if r["games"] == games and r["temperature_plies"] == 0]
+            v = ab.spread_verdict(off, [r["median_plies_per_s"] for r in doc["parent_runs"] if r["games"] == games],
+                                  higher_is_better=True)
+            doc["off_against_parent"][str(games)] = {
+                "this_tree_median_plies_per_s": v["mine"], "parent_median_plies_per_s": v["other"],
+                "parent_spread": v["other_spread"], "this_tree_slower_by": v["behind_by"], "accepted": v["accepted"]}
+            run.save()
     if args.diversity_games > 0:
         for T in temps:
             one("diversity", args.diversity_games, T, None, "diversity")
-    save()
+    run.save()
     print(f"wrote {out}")
 
 

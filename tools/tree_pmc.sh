@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ counter passes over the fused tree kernel k_backup_select_seg (tools/tree_prof.py, single stream,
 # the launches of ply 3), one rocprofv3 run per pass; per-dispatch means in $OUT/summary.txt.
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/tree_pmc}; mkdir -p $OUT
 PY=$(command -v python3)
 SIMS=${SIMS:-400}

@@ -6,7 +6,7 @@ The flagship's engine (3-block network, random-init weights seed 0, fp16x3 split
 fixed deck, staggered starts, compact 0, automatic parts) at 4 096 games (C2) and 65 536 games (C3), with
 reuse_visits 0, 800 and 1200. Every configuration runs in a child process of its own under `timeout` (an engine
 of 65 536 trees of 1 + 40 * 1200 nodes holds 100 GB; nothing of it should outlive its measurement), one at a
-time; a child that is killed, aborts or faults ends the whole run.
+time; the first child without exit status 0 and a result ends the whole run (tools/ab.py).
 
 Per configuration: `--warmup` plies (staggered starts over, trees at their steady-state sizes), then `--reps`
 timed windows of `--plies` plies each, the host's monotonic clock around selfplay_step + sync. Reported: plies/s
@@ -33,13 +33,13 @@ import datetime
 import json
 import shutil
 import statistics
-import subprocess
 import sys
 import time
 from pathlib import Path
 
+import ab
+
 ROOT = Path(__file__).resolve().parents[1]
-FAULTS = {124, 134, 137, 139}  # time limit, abort, kill, segmentation fault: nothing more is started on the GPU
 
 
 def child(args) -> None:
@@ -94,8 +94,8 @@ def child(args) -> None:
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def run_child(args, games, reuse, pkg=None, trace_dir=None, limit=900):
-    """The configuration in a child process under `timeout`; (result dict or None, exit status)."""
+def child_cmd(args, games, reuse, pkg=None, trace_dir=None) -> list:
+    """The command of one configuration's child process; traced, the program goes after `rocprofv3 ... --`."""
     cmd = [sys.executable, str(Path(__file__).resolve()), "--child", "--games", str(games), "--reuse-visits", str(reuse),
            "--sims", str(args.sims), "--warmup", str(args.warmup), "--plies", str(args.plies if not trace_dir else 2),
            "--reps", str(args.reps if not trace_dir else 1)]
@@ -103,14 +103,7 @@ def run_child(args, games, reuse, pkg=None, trace_dir=None, limit=900):
         cmd += ["--pkg", str(pkg)]
     if trace_dir:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "-f", "csv", "-d", str(trace_dir), "--"] + cmd
-    p = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, capture_output=True, text=True)
-    res = None
-    for ln in p.stdout.splitlines():
-        if ln.startswith("RESULT "):
-            res = json.loads(ln[7:])
-    if res is None:
-        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-    return res, p.returncode
+    return cmd
 
 
 def rebase_share(trace_dir: Path):
@@ -155,44 +148,35 @@ def main() -> None:
            "method": "per configuration a child process; warm-up plies, then `reps` windows of `plies_per_window` plies, "
                      "host clock around selfplay_step + sync; plies/s = games x plies / window",
            "runs": [], "parent_runs": [], "traces": []}
-
-    def save():
-        out.parent.mkdir(parents=True, exist_ok=True)
-        out.write_text(json.dumps(doc, indent=1) + "\n")
-
     if args.trace_only:
         if not out.exists():
             raise SystemExit(f"--trace-only adds to an existing file, and {out} does not exist")
         doc = json.loads(out.read_text())
         doc["traces"] = []
+    run = ab.Run(out, doc)
     for games in ([] if args.trace_only else sizes):
         for R in reuse:
-            order = [(None, "runs")]
-            if R == 0 and args.parent:  # this tree and the parent, alternating, twice each
-                order = [(None, "runs"), (Path(args.parent) / "onitama-alphazero_amd", "parent_runs")] * 2
-            for pkg, key in order:
-                res, rc = run_child(args, games, R, pkg=pkg)
-                print(f"games {games} reuse_visits {R} {'parent' if pkg else 'this tree'}: rc {rc} "
-                      f"{res and round(res['median_plies_per_s'], 1)} plies/s", flush=True)
-                if res:
-                    doc[key].append(res)
-                save()
-                if rc in FAULTS or rc < 0 or res is None:
-                    raise SystemExit(f"the child ended with status {rc}: nothing more is started")
+            sides, both = [(None, "runs")], R == 0 and args.parent
+            if both:  # this tree and the parent, alternating, twice each
+                sides.append((Path(args.parent) / "onitama-alphazero_amd", "parent_runs"))
+            for pkg, key in ab.schedule(sides, 2 if both else 1):
+                what = f"games {games} reuse_visits {R} {'parent' if pkg else 'this tree'}"
+                res = run.child(what, child_cmd(args, games, R, pkg=pkg), 900)[-1]
+                print(f"{what}: {round(res['median_plies_per_s'], 1)} plies/s", flush=True)
+                doc[key].append(res)
+                run.save()
     if args.trace or args.trace_only:
         if not shutil.which("rocprofv3"):
             raise SystemExit("--trace needs rocprofv3")
         for R in [r for r in reuse if r > 0]:
             td = Path(args.trace_dir or out.parent / f"tree_reuse_trace_{date}") / f"R{R}"
-            res, rc = run_child(args, sizes[-1], R, trace_dir=td)
-            share = rebase_share(td) if res else None
-            doc["traces"].append({"games": sizes[-1], "reuse_visits": R, "exit": rc, "kernel_trace": share,
+            run.child(f"trace games {sizes[-1]} reuse_visits {R}", child_cmd(args, sizes[-1], R, trace_dir=td), 900)
+            share = rebase_share(td)
+            doc["traces"].append({"games": sizes[-1], "reuse_visits": R, "exit": 0, "kernel_trace": share,
                                   "note": "rocprofv3 --kernel-trace --stats, a run of its own: warm-up plies + 2 plies"})
-            print(f"trace games {sizes[-1]} reuse_visits {R}: rc {rc} {share}", flush=True)
-            save()
-            if rc in FAULTS or rc < 0 or res is None:
-                raise SystemExit(f"the traced child ended with status {rc}: nothing more is started")
-    save()
+            print(f"trace games {sizes[-1]} reuse_visits {R}: {share}", flush=True)
+            run.save()
+    run.save()
     print(f"wrote {out}")
 
 
