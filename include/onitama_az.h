@@ -79,7 +79,8 @@ enum {
     OAZ_ERR_STATE = -5,
     OAZ_ERR_WEIGHTS = -6,
     OAZ_ERR_RANGE = -7,     /* ABI 1 only: ABI 2 recomputes fp16-range tiles instead (oaz_nn_fallbacks) */
-    OAZ_ERR_COMM = -8       /* RCCL communicator error (oaz_comm_*, oaz_allgather_samples) */
+    OAZ_ERR_COMM = -8,      /* RCCL communicator error (oaz_comm_*, oaz_allgather_samples) */
+    OAZ_ERR_INTERNAL = -9   /* a device-side invariant did not hold (oaz_replay_view: the key table overflowed) */
 };
 
 enum { OAZ_EVAL_NN = 0, OAZ_EVAL_HASH = 1 };        /* leaf evaluator (HASH: test evaluator, below) */
@@ -907,6 +908,73 @@ int oaz_reflect_samples(const oaz_sample* in, size_t n, oaz_sample* out);
  * and leaves the uploaded batches as they were. Sample indices must then be below 2^31, which int32 makes them. */
 int oaz_trainer_set_batches_reflect(oaz_trainer* t, const int32_t* idx, const uint8_t* reflect, int n_batches,
                                     int batch);
+
+/* ---- replay buffer: a window of iterations on the device, duplicates merged --------
+ * The training data of the last `window` appends (one append = one segment = one iteration's self-play), kept
+ * on the device in arrival order and capped by `capacity` records; and a merged view of it in which records
+ * of equal position are one record with the mean pi and the mean z. The reference keeps one iteration's Vec
+ * (train.rs:241-250; TrainConfig.buffer_size is only its capacity, train.rs:128) and trains on every copy.
+ *
+ * The merge rule. A record's key is the 22 bytes kings[2], pawns[2], cards[5], to_move of oaz_sample.state (pad
+ * is not part of it). Records of equal key form a group; its representative is the member of smallest arrival
+ * index and its multiplicity m its size. The output holds one record per group, ordered by the representative's
+ * arrival index, and mult[] (uint32). m == 1: the input record byte for byte. m > 1: state = the
+ * representative's 24 bytes (its pad included); for each of the 50 pi entries and for z, with
+ * F(x) = rint((double)x * 2^32) as a 64-bit integer (unsigned for pi, signed for z; round half to even) and
+ * S = the integer sum of F(x) over the group, the entry is (float)((double)S / ((double)m * 4294967296.0)): one
+ * correctly rounded double division, then round to nearest even to float. Integer sums do not depend on the
+ * order, so the device's bytes are the host's. pi is assumed to lie in [0, 1] and z in [-1, 1] (what self-play
+ * writes); values outside, NaN included, are not checked and give unspecified entries in merged records only.
+ *
+ * The window. Each append is one segment, n == 0 included (an iteration without records still ages the window).
+ * A segment of more than `capacity` records is OAZ_ERR_CAPACITY and changes nothing. After an append the oldest
+ * segments are dropped while there are more than `window` of them, then while the records exceed `capacity`
+ * and more than one segment is left. `tag` (the loop passes the iteration number) is kept with the segment and
+ * appears in error texts only.
+ *
+ * Threading as the engine's: one thread at a time per buffer; every entry runs on the buffer's device and
+ * restores the calling thread's current device. */
+typedef struct oaz_replay oaz_replay;
+typedef struct oaz_replay_config {
+    uint64_t capacity;     /* records; default 180000 = TrainConfig.buffer_size (train.rs:128); < 2^31 */
+    int32_t  window;       /* segments (iterations) kept; default 1 */
+    int32_t  device;
+    uint32_t table_slots;  /* 0 = auto: smallest power of two >= 2 n; else a power of two > n of the view being built, OAZ_ERR_ARG otherwise */
+    uint32_t pad;
+} oaz_replay_config; /* 24 bytes */
+typedef struct oaz_replay_stats {
+    uint64_t segments, records;                 /* in the window now */
+    uint64_t unique, max_mult;                  /* of the last merged view */
+    uint64_t appended, evicted;                 /* records, since creation */
+    uint64_t probes;                            /* key comparisons of the last merge */
+} oaz_replay_stats; /* 56 bytes */
+
+void oaz_replay_config_default(oaz_replay_config* cfg);
+/* NULL (oaz_last_error): capacity 0 or >= 2^31, window < 1, no such device. */
+oaz_replay* oaz_replay_create(const oaz_replay_config* cfg);
+void oaz_replay_destroy(oaz_replay* r);
+/* One segment from host memory, from device memory of the buffer's device (read on the buffer's stream; the
+ * caller's writes to it are complete), or all of an engine's buffered samples device to device (the engine's
+ * buffer is empty afterwards; *n_out, optional, = records taken; an engine on another device is OAZ_ERR_ARG). */
+int oaz_replay_append_host(oaz_replay* r, const oaz_sample* host, size_t n, int64_t tag);
+int oaz_replay_append_device(oaz_replay* r, const oaz_sample* dev, size_t n, int64_t tag);
+int oaz_replay_append_engine(oaz_replay* r, oaz_engine* eng, int64_t tag, size_t* n_out);
+/* The window as device memory. merge == 0: its records, contiguous, in arrival order; *dev_mult = NULL.
+ * merge == 1: the merged records and their multiplicities (the rule above). Returns after the buffer's stream
+ * is synchronised, so work on any other stream may read; the pointers hold until the next append, view, fetch
+ * or destroy. An empty window gives *n = 0 and launches nothing. dev_mult may be NULL. */
+int oaz_replay_view(oaz_replay* r, int merge, const oaz_sample** dev, size_t* n, const uint32_t** dev_mult);
+/* oaz_replay_view copied to host memory: out[cap], mult[cap] (optional; all 1 with merge == 0).
+ * OAZ_ERR_CAPACITY when the view holds more than cap records; *n_out is the view's size either way. */
+int oaz_replay_fetch(oaz_replay* r, int merge, oaz_sample* out, uint32_t* mult, size_t cap, size_t* n_out);
+int oaz_replay_stats_get(oaz_replay* r, oaz_replay_stats* out);
+/* The last merged view's device time by phase, in milliseconds (HIP events on the buffer's stream): key pass,
+ * insert, lookup, scan + compact, group (count, scan, member lists), emit. All 0 before the first merge. */
+enum { OAZ_REPLAY_PHASES = 6 };
+int oaz_replay_merge_times(oaz_replay* r, double ms[OAZ_REPLAY_PHASES]);
+/* The merge rule in plain C++ on the host (no GPU): out[n], mult[n] (optional), *n_out = groups. out may not
+ * overlap in. */
+int oaz_replay_merge_host(const oaz_sample* in, size_t n, oaz_sample* out, uint32_t* mult, size_t* n_out);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,9 @@ from .pure_mcts import Mcts, pure_mcts_search, pure_mcts_search_each
 from .alpha_beta import AlphaBeta, alpha_beta_generate_move, alpha_beta_search
 from .tournament import Tournament
 from .parameter_check import ParameterCheck
-from .trainer import Trainer, choose_batches_doubled, choose_reflect, train_epochs, train_epochs_dp
+from .replay import ReplayBuffer
+from .trainer import (Trainer, choose_batches_doubled, choose_reflect, train_epochs, train_epochs_device,
+                      train_epochs_dp, train_epochs_dp_device)
 from .train_loop import LoopConfig, Stats, train
 
 __all__ = [
@@ -32,5 +34,5 @@ __all__ = [
     "LoopConfig", "Stats", "train", "AlphaBeta", "alpha_beta_search", "NativeRandomAgent", "native_fight",
     "alpha_beta_generate_move", "Tournament", "pure_mcts_search_each", "ParameterCheck",
     "reflect_square", "reflect_card", "reflect_states", "reflect_moves", "reflect_samples", "choose_reflect",
-    "choose_batches_doubled", "train_epochs_dp",
+    "choose_batches_doubled", "train_epochs_dp", "ReplayBuffer", "train_epochs_device", "train_epochs_dp_device",
 ]

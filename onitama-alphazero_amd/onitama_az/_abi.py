@@ -24,6 +24,7 @@ ERR_RANGE = -7  # OAZ_ERR_RANGE (ABI 1 only; ABI 2 recomputes fp16-range tiles, 
 ERR_CAPACITY = -4
 ERR_STATE = -5
 ERR_COMM = -8
+ERR_INTERNAL = -9
 ABI_VERSION = 5
 MAX_MOVES = 40
 
@@ -288,6 +289,17 @@ class oaz_comm_stats(C.Structure):
     ]
 
 
+class oaz_replay_config(C.Structure):  # 24 bytes
+    _fields_ = [("capacity", C.c_uint64), ("window", C.c_int32), ("device", C.c_int32), ("table_slots", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class oaz_replay_stats(C.Structure):  # 56 bytes
+    _fields_ = [(k, C.c_uint64) for k in ("segments", "records", "unique", "max_mult", "appended", "evicted", "probes")]
+
+
+REPLAY_PHASES = ("key", "insert", "lookup", "scan", "group", "emit")  # oaz_replay_merge_times
+
 assert C.sizeof(oaz_state) == 24
 assert C.sizeof(oaz_move) == 4
 assert C.sizeof(oaz_node) == 32
@@ -298,6 +310,7 @@ assert oaz_config.temperature_plies.offset == 69 and oaz_config.seed.offset == 7
 assert oaz_config.leaf_batch.offset == 70
 assert C.sizeof(oaz_arena_agent) == 88 and C.sizeof(oaz_arena_config) == 40 and C.sizeof(oaz_fight_stats) == 96
 assert C.sizeof(oaz_arena_slots_stats) == 40
+assert C.sizeof(oaz_replay_config) == 24 and C.sizeof(oaz_replay_stats) == 56
 
 STATE_DTYPE = np.dtype(
     [("kings", "<u4", 2), ("pawns", "<u4", 2), ("cards", "u1", 5), ("to_move", "u1"), ("pad", "u1", 2)]
@@ -435,6 +448,17 @@ _PROTOS = {
     "oaz_reflect_samples_host": (C.c_int, [_VOIDP, C.c_size_t, _VOIDP]),
     "oaz_reflect_samples": (C.c_int, [_VOIDP, C.c_size_t, _VOIDP]),
     "oaz_trainer_set_batches_reflect": (C.c_int, [_VOIDP, _VOIDP, _VOIDP, C.c_int, C.c_int]),
+    "oaz_replay_config_default": (None, [_P(oaz_replay_config)]),
+    "oaz_replay_create": (_VOIDP, [_P(oaz_replay_config)]),
+    "oaz_replay_destroy": (None, [_VOIDP]),
+    "oaz_replay_append_host": (C.c_int, [_VOIDP, _VOIDP, C.c_size_t, C.c_int64]),
+    "oaz_replay_append_device": (C.c_int, [_VOIDP, _VOIDP, C.c_size_t, C.c_int64]),
+    "oaz_replay_append_engine": (C.c_int, [_VOIDP, _VOIDP, C.c_int64, _P(C.c_size_t)]),
+    "oaz_replay_view": (C.c_int, [_VOIDP, C.c_int, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p)]),
+    "oaz_replay_fetch": (C.c_int, [_VOIDP, C.c_int, _VOIDP, _VOIDP, C.c_size_t, _P(C.c_size_t)]),
+    "oaz_replay_stats_get": (C.c_int, [_VOIDP, _P(oaz_replay_stats)]),
+    "oaz_replay_merge_times": (C.c_int, [_VOIDP, _P(C.c_double * 6)]),
+    "oaz_replay_merge_host": (C.c_int, [_VOIDP, C.c_size_t, _VOIDP, _VOIDP, _P(C.c_size_t)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

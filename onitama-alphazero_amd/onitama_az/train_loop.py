@@ -29,7 +29,8 @@ from .engine import Engine
 from .evaluator import EvaluatorConfig, Evaluator, PitStatistics
 from .game import Deck
 from .mcts import AlphaZeroMctsConfig, ConvResNet, ConvResNetConfig, Options
-from .trainer import Trainer, train_epochs, train_epochs_dp
+from .replay import ReplayBuffer
+from .trainer import Trainer, train_epochs, train_epochs_device, train_epochs_dp, train_epochs_dp_device
 from .weights import checkpoint_path, random_weights, save_blob_ot
 
 
@@ -60,6 +61,13 @@ class LoopConfig:  # TrainConfig, train.rs:100-154 (defaults of Default::default
     # 1 = every drawn sample reflected with probability 1/2; 2 = the buffer together with its reflection (twice
     # the steps per epoch). Self-play, the pit and the arena are not touched.
     reflect_augment: int = 0
+    # the replay buffer (onitama_az.replay). Any of the three away from its default puts the
+    # iteration's samples into a device ReplayBuffer(capacity=buffer_size, window=replay_iterations) straight from
+    # the engine and trains on its view, bound in device memory; all three at their defaults: the loop as it was
+    # (one iteration's samples through the host, every copy trained on), as the reference.
+    replay_iterations: int = 1  # train on the last N iterations' samples (capped by buffer_size)
+    merge_duplicates: bool = False  # records of equal position become one, with the mean pi and the mean z
+    device_replay: bool = False  # the replay path with a window of one and without merging: the same training
 
 
 @dataclass
@@ -89,12 +97,13 @@ def _bcast(obj, world: int):
 
 def train(config: LoopConfig, folder: Optional[str] = None, options: Options = None,
           initial_weights: Optional[np.ndarray] = None, eval_sims: int = 400, rank: int = 0, world: int = 1,
-          comm=None, on_iteration=None) -> Stats:
+          comm=None, on_iteration=None, replay: Optional[ReplayBuffer] = None) -> Stats:
     """train.rs:158-412. Returns the statistics (also written to <folder>/stats.json by rank 0).
     world > 1: an initialised torch.distributed group (rank, world); `comm` (onitama_az.dist.Comm,
     RCCL) carries the sample all-gather and the gradient all-reduce, without it they go over the
     default group through host copies (gloo tests / one-GPU rehearsals). on_iteration(it, new, best),
-    if given, sees each iteration's trained and best weights (tests)."""
+    if given, sees each iteration's trained and best weights (tests). replay: the caller's ReplayBuffer for the
+    replay path (left open; a caller that wants to look into the window), otherwise the loop makes its own."""
     from .dist import allgather_samples
     options = options or Options()
     blocks = config.model_config.resnet_block_amnt
@@ -108,6 +117,11 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
     ratings = [(800.0, 800.0), (800.0, 800.0), (800.0, 800.0)]  # vs best, random, mcts (train.rs:188-205)
     n_games = config.self_play_game_amnt * config.thread_amnt
     mc = config.mcts_config
+    on_replay = config.replay_iterations != 1 or config.merge_duplicates or config.device_replay
+    own_replay = None
+    if on_replay and replay is None:
+        replay = own_replay = ReplayBuffer(capacity=config.buffer_size, window=config.replay_iterations,
+                                           device=options.device)
     with Trainer(blocks=blocks, max_batch=config.train_batch_size, learning_rate=config.learning_rate,
                  weight_decay=config.l2_const, device=options.device) as tr:
         tr.set_weights(weights)
@@ -123,15 +137,35 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
                 kw.update(fixed_deck=1, deck=config.deck.indices())
             with Engine(device=options.device, **kw) as eng:
                 eng.load_weights(best)
-                if world == 1:
+                if on_replay and world == 1:  # the samples never leave the device
+                    eng.selfplay_run(n_games, cap=0)
+                    n_new = replay.append_engine(eng, it)
+                elif world == 1:
                     samples, _ = eng.selfplay_run(n_games, cap=n_games * (config.max_plies + 2))
                 else:  # this rank's share, left on the device, then every rank's samples in rank order
                     import torch
                     eng.selfplay_run(n_games, cap=0)
                     samples = allgather_samples(eng, world, torch.device("cuda", options.device), comm=comm)
-            stats.games_played.append({"games_amnt": n_games, "positions_retrieved": int(len(samples))})
+            if on_replay:
+                if world > 1:  # the gathered host array (device to device from the gather: DESIGN.md section 5h)
+                    replay.append(samples, it)
+                    n_new = len(samples)
+                stats.games_played.append({"games_amnt": n_games, "positions_retrieved": int(n_new)})
+                ptr, n_view, _ = replay.view(config.merge_duplicates)
+                stats.games_played[-1]["window_records"] = int(replay.stats().records)
+                if config.merge_duplicates:
+                    stats.games_played[-1]["unique_records"] = int(n_view)
+            else:
+                stats.games_played.append({"games_amnt": n_games, "positions_retrieved": int(len(samples))})
             # training epochs (train.rs:257-325)
-            if world == 1:
+            if on_replay and world == 1:
+                hist = train_epochs_device(tr, ptr, n_view, epochs=config.training_epochs, batch=config.train_batch_size,
+                                           seed=config.seed + 1000 + it, reflect=config.reflect_augment)
+            elif on_replay:
+                hist = train_epochs_dp_device(tr, ptr, n_view, epochs=config.training_epochs,
+                                              batch=config.train_batch_size, seed=config.seed + 1000 + it, rank=rank,
+                                              world=world, comm=comm, reflect=config.reflect_augment)
+            elif world == 1:
                 hist = train_epochs(tr, samples, epochs=config.training_epochs, batch=config.train_batch_size,
                                     seed=config.seed + 1000 + it, reflect=config.reflect_augment)
             else:
@@ -171,4 +205,6 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
                 stats.save(os.path.join(folder, "stats.json"))
             if on_iteration is not None:
                 on_iteration(it, new, best)
+    if own_replay is not None:
+        own_replay.close()
     return stats

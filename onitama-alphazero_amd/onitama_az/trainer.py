@@ -199,14 +199,29 @@ def train_epochs(trainer: Trainer, samples: np.ndarray, epochs: int = 10, batch:
     reflected with probability 1/2, the flags from a generator of their own (seed and REFLECT_TAG), the index
     stream and the epoch length unchanged. 2 = the buffer together with its reflection: every batch a draw
     without replacement from the 2 n entries, 2 n // batch batches per epoch."""
+    trainer.load_samples(samples)
+    return _epochs(trainer, len(samples), epochs, batch, seed, reflect)
+
+
+def train_epochs_device(trainer: Trainer, ptr: int, n: int, epochs: int = 10, batch: int = 512, seed: int = 0,
+                        reflect: int = 0) -> List[EpochLoss]:
+    """train_epochs on n records that are already in device memory at `ptr` (a ReplayBuffer view; the trainer's
+    device): they are bound (oaz_trainer_bind_device_samples), never copied, and the index and flag streams are
+    those train_epochs draws for the same n, seed and reflect. The memory stays the caller's and stays as it is
+    until the call returns."""
+    trainer.bind_device_samples(ptr, n)
+    return _epochs(trainer, int(n), epochs, batch, seed, reflect)
+
+
+def _epochs(trainer, n_samples: int, epochs: int, batch: int, seed: int, reflect: int) -> List[EpochLoss]:
+    """The epochs of train_epochs on the samples the trainer holds."""
     rng = np.random.default_rng(seed)
     flag_rng = np.random.default_rng([REFLECT_TAG, seed])
-    trainer.load_samples(samples)
     out: List[EpochLoss] = []
     for _ in range(epochs):
-        if len(samples) < batch:
+        if n_samples < batch:
             break
-        idx, flags = epoch_batches(rng, flag_rng, len(samples), batch, reflect)
+        idx, flags = epoch_batches(rng, flag_rng, n_samples, batch, reflect)
         n = len(idx)
         _set_batches(trainer, idx, flags)
         trainer.train(0, n)
@@ -247,6 +262,19 @@ def train_epochs_dp(trainer: Trainer, samples: np.ndarray, epochs: int, batch: i
     statistics are averaged over ranks after each epoch, and the reported losses are the global
     ones, so every rank ends each epoch with identical weights and statistics. reflect: as train_epochs; every
     rank draws the same flags and takes the column slice of them that it takes of the indices."""
+    return _dp(trainer, lambda: trainer.load_samples(samples), len(samples), epochs, batch, seed, rank, world, comm,
+               reflect)
+
+
+def train_epochs_dp_device(trainer: Trainer, ptr: int, n: int, epochs: int, batch: int, seed: int, rank: int,
+                           world: int, comm=None, reflect: int = 0) -> List[EpochLoss]:
+    """train_epochs_dp on n records bound in device memory (train_epochs_device's terms): every rank binds its own
+    copy of the same records."""
+    return _dp(trainer, lambda: trainer.bind_device_samples(ptr, n), int(n), epochs, batch, seed, rank, world, comm,
+               reflect)
+
+
+def _dp(trainer, attach, n_samples, epochs, batch, seed, rank, world, comm, reflect) -> List[EpochLoss]:
     import torch
     assert batch % world == 0 and (batch // world) % 16 == 0
     shard = batch // world
@@ -255,13 +283,16 @@ def train_epochs_dp(trainer: Trainer, samples: np.ndarray, epochs: int, batch: i
     # leave the all-reduce unordered against backward / apply)
     ts = torch.cuda.Stream()
     with torch.cuda.stream(ts):
-        out = _epochs_dp(trainer, samples, epochs, batch, seed, rank, world, comm, shard, ts.cuda_stream, reflect)
+        out = _epochs_dp(trainer, attach, n_samples, epochs, batch, seed, rank, world, comm, shard, ts.cuda_stream,
+                         reflect)
     trainer.sync()
     trainer.set_stream(None)
     return out
 
 
-def _epochs_dp(trainer, samples, epochs, batch, seed, rank, world, comm, shard, stream, reflect=0) -> List[EpochLoss]:
+def _epochs_dp(trainer, attach, n_samples, epochs, batch, seed, rank, world, comm, shard, stream,
+               reflect=0) -> List[EpochLoss]:
+    """attach(): makes the n_samples records the trainer's (load_samples or bind_device_samples)."""
     import torch
     trainer.set_stream(stream)
     dev = f"cuda:{torch.cuda.current_device()}"
@@ -271,12 +302,12 @@ def _epochs_dp(trainer, samples, epochs, batch, seed, rank, world, comm, shard, 
     bn = torch.empty(nbn, dtype=torch.float32, device=dev)
     rng = np.random.default_rng(seed)
     flag_rng = np.random.default_rng([REFLECT_TAG, seed])
-    trainer.load_samples(samples)
+    attach()
     out: List[EpochLoss] = []
     for _ in range(epochs):
-        if len(samples) < batch:
+        if n_samples < batch:
             break
-        idx, flags = epoch_batches(rng, flag_rng, len(samples), batch, reflect, rank, world)
+        idx, flags = epoch_batches(rng, flag_rng, n_samples, batch, reflect, rank, world)
         nb = len(idx)
         assert idx.shape[1] == shard
         _set_batches(trainer, idx, flags)
