@@ -304,6 +304,10 @@ double oaz_root_noise(uint64_t seed, uint64_t game_id, uint32_t ply, uint32_t si
  * nothing (K <= 0, null visits or S == 0: the pass or the most visited child is played, as without temperature).
  * T does not enter: whether ply < T is the caller's question. */
 int oaz_temperature_pick(uint64_t seed, uint64_t game_id, uint32_t ply, const uint32_t* visits, int K);
+/* The playout cap rule (oaz_selfplay_set_playout_cap), restated on the host; needs no device. Ply `ply` of global
+ * game `game_id` is a full ply iff word 0 of Philox(seed; game_id lo, game_id hi, 0x50434150, ply), shifted right by
+ * 16, is below full_per_65536. Returns 1 (full) or 0 (fast); OAZ_ERR_ARG for full_per_65536 > 65536. */
+int oaz_playout_cap_full(uint64_t seed, uint64_t game_id, uint32_t ply, uint32_t full_per_65536);
 
 /* ---- rules on the GPU (bit-exact with the reference) ---------------------------- */
 /* Legal moves of s[i].to_move. masks[i][k][from] = destination mask of own piece on
@@ -452,6 +456,23 @@ int oaz_selfplay_stats_get(oaz_engine* eng, oaz_selfplay_stats* out);
 /* Self-play temperature, since creation or the last oaz_selfplay_reset: out[0] = plies whose move was drawn from
  * the visits, out[1] = those whose drawn child is not the most visited one (both 0 with temperature_plies == 0). */
 int oaz_selfplay_temperature_stats(oaz_engine* eng, uint64_t out[2]);
+/* Playout cap randomization, an engine setting for the following self-play: a ply that
+ * oaz_playout_cap_full(cfg.seed, game id, ply, full_per_65536) calls full is searched with cfg.sims playouts and
+ * recorded, every other ply with fast_sims playouts and only played. Both kinds use cfg.c_puct and cfg.train_noise
+ * and play the move the engine would play from that tree (the temperature draw, else the last maximum of the visits,
+ * the pass at a root without a child). A finished game's records are its full plies in ply order; a game without one
+ * gives no record and still counts in games_finished. fast_sims = 0 turns the cap off. Setting or changing the cap
+ * ends the running games: the next oaz_selfplay_step starts from a reset, as on a fresh engine. A capped ply runs on
+ * the per-simulation-step kernels with leaf compaction on, whatever cfg.compact and cfg.step_kernels say, so that
+ * the games that stopped leave the network's batch. The cap's device buffers (7 bytes per slot) are allocated by
+ * the first call that sets one. oaz_search, oaz_search_resume, the arena and the agents ignore the cap.
+ * OAZ_ERR_ARG: fast_sims < 0, full_per_65536 outside 0 .. 65536, a null engine. OAZ_ERR_STATE (nothing else runs
+ * instead): an engine with reuse_visits > 0, leaf_batch > 0 or a search-time budget; and from oaz_selfplay_step
+ * while a cap is set and fast_sims >= cfg.sims, or a search-time budget has been set since. */
+int oaz_selfplay_set_playout_cap(oaz_engine* eng, int fast_sims, int full_per_65536);
+/* out[0] = full plies, out[1] = fast plies played since the last reset (both 0 without a cap);
+ * oaz_selfplay_stats.search.sims is then out[0] * cfg.sims + out[1] * fast_sims. */
+int oaz_selfplay_playout_cap_stats(oaz_engine* eng, uint64_t out[2]);
 /* Copy up to cap buffered samples to host memory and drop them from the device buffer. */
 int oaz_samples_fetch(oaz_engine* eng, oaz_sample* out, size_t cap, size_t* n_out);
 /* Device-to-device copy of up to cap_bytes/sizeof(oaz_sample) buffered samples into a

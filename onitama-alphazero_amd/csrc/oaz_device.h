@@ -355,6 +355,17 @@ OAZ_HD int temperature_draw_child(uint64_t seed, uint64_t game, uint32_t ply, co
     return -1;  // (never reached: r < S)
 }
 
+// ---- playout cap randomization (oaz_selfplay_set_playout_cap) ---------------------
+// Ply `ply` of global game `game` is a full ply (searched with cfg.sims playouts and recorded) iff the high 16
+// bits of word 0 of Philox(seed; game lo, game hi, 0x50434150 "PCAP", ply) are below P, the full share in
+// 1/65 536; every other ply is a fast one (fast_sims playouts, played only). The temperature draw's generator
+// and counter layout under a tag of its own (>= 2^24 as well: no root-noise word equals it).
+constexpr uint32_t kPlayoutCapTag = 0x50434150u;
+OAZ_HD bool playout_cap_full(uint64_t seed, uint64_t game, uint32_t ply, uint32_t P) {
+    const u32x4 w = philox(seed, (uint32_t)game, (uint32_t)(game >> 32), kPlayoutCapTag, ply);
+    return (w.x >> 16) < P;
+}
+
 // ---- left-right reflection -------------------------------------------------------
 // The reflection in the c-file: square i -> R(i) = 5 (i / 5) + 4 - i % 5, and card k -> C[k], the card whose
 // attack map is the reflected one: reflect_bits(ATTACK[c][k][f]) == ATTACK[c][C[k]][R(f)] for both colours and

@@ -414,6 +414,14 @@ struct oaz_engine {
     DevBuf<uint64_t> par_stats;
     uint32_t par_G = 0;           // roots of the last leaf-parallel search (0: none yet)
     DevBuf<uint64_t> temp_cnt;    // self-play temperature (cfg.temperature_plies > 0 only): oaz_selfplay_temperature_stats
+    // playout cap randomization (oaz_selfplay_set_playout_cap; nothing is allocated before a cap is set, and the
+    // buffers stay once made): the cap, the per-slot full flag and the two phase masks ([3][G]), the per-slot
+    // record count and the two oaz_selfplay_playout_cap_stats counters (CapView, oaz_kernels.h)
+    int32_t pc_fast = 0;          // fast_sims (0: no cap)
+    uint32_t pc_share = 0;        // the full share in 1/65 536
+    DevBuf<uint8_t> pc_flags;
+    DevBuf<uint32_t> pc_nrec;
+    DevBuf<unsigned long long> pc_cnt;
     uint32_t searched = 0;        // games whose trees are the last oaz_search / oaz_search_resume's (0: self-play ran since)
     int64_t tree_visits = 0;      // the most root visits any of those trees can hold by now
     bool ply_trees = false;       // the trees are the previous self-play ply's (cleared by oaz_selfplay_reset and any search)
@@ -477,6 +485,17 @@ static SlotView slot_view(oaz_engine* e) {
     s.quota = e->quota;
     s.stagger = e->quota ? 0u : (uint32_t)(e->cfg.stagger > 0 ? e->cfg.stagger : 0);
     return s;
+}
+
+static CapView cap_view(const oaz_engine* e) {
+    CapView c;
+    c.full = e->pc_flags;
+    c.fast = e->pc_flags + e->G;
+    c.fullm = e->pc_flags + 2 * (size_t)e->G;
+    c.nrec = e->pc_nrec;
+    c.cnt = e->pc_cnt;
+    c.P = e->pc_share;
+    return c;
 }
 
 static SearchParams search_params(const oaz_engine* e) {
@@ -1237,24 +1256,87 @@ static int run_chunks(oaz_engine* e, const Search& S, bool grp) {
     return P.join();
 }
 
+// The two budget phases of a capped self-play ply (playout cap randomization): the playouts
+// of a fast ply and the two masks launch_playout_cap_masks made of the slots' `active` bytes for this ply.
+struct PlyCap {
+    uint32_t n;            // fast_sims, 1 <= n < S.sims
+    const uint8_t* fast;   // [G] active and a fast ply: these games stop after simulation n - 1
+    const uint8_t* fullm;  // [G] active and a full ply: these go on to S.sims
+};
+
+// A capped ply on the per-step loop, leaf compaction on: run_chunks' per-step branch with the mask changing once.
+//   steps 0 .. n-1       every active game (S.active), as without a cap;
+//   expand/backup        simulation n - 1's, for the games that stop (fast), on each part's own stream and queued
+//                        before step n: it reads the rows step n - 1's compaction left in `slot`, which step n's
+//                        compaction rewrites;
+//   steps n .. sims-1    the full games (fullm): to every kernel a fast game is now an idle slot, so its `need` byte
+//                        is 0 and its leaf is in no network tile. Step n's fused backup/select backs simulation
+//                        n - 1 up for exactly the games it then walks;
+//   expand/backup        the last simulation's, for the full games.
+// The host does not know whether any game's ply is a full one, so the second phase is always launched; with no full
+// game its tree kernels find idle slots only and the network's workgroups exit on empty buckets. The root-noise
+// chunks that begin at or after simulation n are drawn for the full games only.
+static int run_capped(oaz_engine* e, const Search& S0, const PlyCap& pc) {
+    Search S = S0;  // (the ring's producer reads S.active when a chunk is launched)
+    Parts P(e, S, game_parts(e, S.t.G));
+    const NoiseRing ring{e, S, P, e->noise_chunk};
+    const uint32_t nchunks = (S.sims + ring.chunk - 1) / ring.chunk;
+    e->times.parts = (uint64_t)P.n;
+    const auto backup = [&](const uint8_t* mask) {
+        e->timing_skip = false;
+        for (int h = 0; h < P.n; ++h) {
+            const Parts::Part& p = P.part[h];
+            if (int rc = timed(e, K_EXPAND, p.t.G, [&] {
+                    return launch_expand_backup(p.t, p.roots, mask + p.g0, p.pol, p.val, p.st);
+                }, p.st))
+                return rc;
+        }
+        return 0;
+    };
+    if (int rc = ring.produce(0)) return rc;
+    if (int rc = P.fork()) return rc;
+    bool spent = false;  // (never set: a capped ply has no search-time budget)
+    for (uint32_t c = 0; c < nchunks; ++c) {
+        if ((c + 1) * ring.chunk >= pc.n) S.active = pc.fullm;
+        if (int rc = ring.produce(c + 1)) return rc;
+        if (int rc = ring.wait(c)) return rc;
+        for (uint32_t s = c * ring.chunk, s1 = std::min(s + ring.chunk, S.sims); s < s1; ++s) {
+            if (s == pc.n) {
+                if (int rc = backup(pc.fast)) return rc;
+                for (int h = 0; h < P.n; ++h) P.part[h].active = pc.fullm + P.part[h].g0;
+            }
+            if (int rc = sim_step(e, S, P, ring, s, &spent)) return rc;
+        }
+        if (int rc = ring.release(c)) return rc;
+    }
+    if (int rc = backup(pc.fullm)) return rc;
+    return P.join();
+}
+
 // The simulations of one move on the path that fits (search_path). On an error the game parts' streams are
 // joined into the engine stream anyway (all of them, whatever the number of parts was: the drivers' early
 // returns skip the join), so oaz_sync and buffer reuse after an error wait for them.
+// pc (a capped self-play ply): run_capped, whatever cfg.compact and cfg.step_kernels say; the forced path is only
+// there for the work it saves.
 static int run_sims(oaz_engine* e, const TreeView& t, const oaz_state* roots, const uint8_t* active,
-                    const uint64_t* gids, const uint32_t* plies, bool kept_trees = false) {
+                    const uint64_t* gids, const uint32_t* plies, bool kept_trees = false, const PlyCap* pc = nullptr) {
     const bool budget = e->cfg.search_time_ns > 0, noise = e->cfg.train_noise && e->noise;
-    const SearchPath path = search_path(e, t.G, noise, kept_trees);
+    const SearchPath path = pc ? PATH_STEPS : search_path(e, t.G, noise, kept_trees);
     const NNView w = nn_view(e, nullptr);
     Search S{t, roots, active, gids, plies, search_params(e), (uint32_t)e->cfg.sims, noise,
              e->cfg.evaluator == OAZ_EVAL_HASH ? nullptr : &w, budget ? e->deadline.get() : nullptr,
              budget ? e->sims_run.get() : nullptr};
-    if (!compact_leaves(e, t.G)) {  // (always so on the one-launch paths) rows = game ids
+    if (!pc && !compact_leaves(e, t.G)) {  // (always so on the one-launch paths) rows = game ids
         S.t.need = nullptr;
         S.t.slot = nullptr;
     }
     e->last = LastSearch{t.G};
     int rc = path == PATH_STEPS ? 0 : arm_device_budget(e, t.G);
-    if (!rc) rc = path == PATH_PAR ? search_par(e, S) : path == PATH_LAT ? search_lat(e, S) : run_chunks(e, S, path == PATH_GRP);
+    if (!rc)
+        rc = pc                 ? run_capped(e, S, *pc)
+             : path == PATH_PAR ? search_par(e, S)
+             : path == PATH_LAT ? search_lat(e, S)
+                                : run_chunks(e, S, path == PATH_GRP);
     if (rc) {
         const std::string msg = g_err;
         for (int h = 1; h < kMaxParts; ++h)
@@ -1431,6 +1513,10 @@ extern "C" int oaz_selfplay_reset(oaz_engine* e) {
     e->out_read = 0;
     if (e->reuse_cnt) HIP_TRY(hipMemsetAsync(e->reuse_cnt, 0, 4 * sizeof(uint64_t), e->stream));
     if (e->temp_cnt) HIP_TRY(hipMemsetAsync(e->temp_cnt, 0, 2 * sizeof(uint64_t), e->stream));
+    if (e->pc_nrec) {
+        HIP_TRY(hipMemsetAsync(e->pc_nrec, 0, (size_t)e->G * sizeof(uint32_t), e->stream));
+        HIP_TRY(hipMemsetAsync(e->pc_cnt, 0, 2 * sizeof(unsigned long long), e->stream));
+    }
     e->ply_trees = false;
     e->searched = 0;
     HIP_TRY(launch_selfplay_reset(t, slot_view(e), e->stream));
@@ -1442,12 +1528,20 @@ extern "C" int oaz_selfplay_reset(oaz_engine* e) {
 extern "C" int oaz_selfplay_step(oaz_engine* e, int moves) {
     if (!e || moves < 0) return oaz_set_err(OAZ_ERR_ARG, "selfplay_step: bad arguments");
     if (int rc = par_no_selfplay(e, "selfplay_step")) return rc;
+    const bool capped = e->pc_fast > 0;
+    if (capped && e->pc_fast >= e->cfg.sims)
+        return oaz_set_err(OAZ_ERR_STATE, "selfplay_step: the playout cap's fast_sims=%d is not below sims=%d", e->pc_fast,
+                           e->cfg.sims);
+    if (capped && e->cfg.search_time_ns > 0)
+        return oaz_set_err(OAZ_ERR_STATE, "selfplay_step: a playout cap does not run with a search-time budget");
     if (!e->selfplay_ready)
         if (int rc = oaz_selfplay_reset(e)) return rc;
     OAZ_ON_DEVICE(e->device);
     const TreeView t = tree_view(e, e->G);
     const SlotView sv = slot_view(e);
     const uint32_t temp_plies = e->cfg.temperature_plies;  // 0: the launches of an engine without temperature
+    const CapView cv = cap_view(e);  // (all null without a cap)
+    const PlyCap pc{(uint32_t)e->pc_fast, cv.fast, cv.fullm};
     for (int m = 0; m < moves; ++m) {
         if (int rc = begin_budget(e)) return rc;
         const bool reuse = e->cfg.reuse_visits > 0;
@@ -1458,10 +1552,12 @@ extern "C" int oaz_selfplay_step(oaz_engine* e, int moves) {
             HIP_TRY(launch_selfplay_rebase(t, sv, e->ply_trees, e->sims_cap, e->cfg.reuse_visits, temp_plies, e->reuse_cnt,
                                            e->stream));
         e->ply_trees = false;
-        if (int rc = run_sims(e, t, e->root, e->active, e->game_id, e->ply, reuse)) return rc;
+        if (capped) HIP_TRY(launch_playout_cap_masks(sv, cv, e->stream));  // this ply's full flags and phase masks
+        if (int rc = run_sims(e, t, e->root, e->active, e->game_id, e->ply, reuse, capped ? &pc : nullptr)) return rc;
         if (int rc = timed(e, K_FINALIZE, e->G, [&] {
-                return temp_plies ? launch_selfplay_move_temp(t, sv, temp_plies, e->temp_cnt, e->stream)
-                                  : launch_selfplay_move(t, sv, e->stream);
+                return capped       ? launch_selfplay_move_cap(t, sv, cv, temp_plies, e->temp_cnt, e->stream)
+                       : temp_plies ? launch_selfplay_move_temp(t, sv, temp_plies, e->temp_cnt, e->stream)
+                                    : launch_selfplay_move(t, sv, e->stream);
             }))
             return rc;
         e->ply_trees = true;
@@ -1518,6 +1614,57 @@ extern "C" int oaz_selfplay_temperature_stats(oaz_engine* e, uint64_t out[2]) {
     if (!e->temp_cnt) return 0;
     OAZ_ON_DEVICE(e->device);
     HIP_TRY(hipMemcpyAsync(out, e->temp_cnt, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// ---- playout cap randomization ---------------------------------------------------------
+extern "C" int oaz_playout_cap_full(uint64_t seed, uint64_t game_id, uint32_t ply, uint32_t full_per_65536) {
+    if (full_per_65536 > 65536u)
+        return oaz_set_err(OAZ_ERR_ARG, "playout_cap_full: full_per_65536=%u > 65536", full_per_65536);
+    return playout_cap_full(seed, game_id, ply, full_per_65536) ? 1 : 0;
+}
+
+// An engine setting, as oaz_set_search_time is (oaz_config keeps its size). The combinations the two-phase ply does
+// not run are refused here or at the step; nothing else runs in its place.
+extern "C" int oaz_selfplay_set_playout_cap(oaz_engine* e, int fast_sims, int full_per_65536) {
+    if (!e) return oaz_set_err(OAZ_ERR_ARG, "set_playout_cap: null");
+    if (fast_sims < 0 || full_per_65536 < 0 || full_per_65536 > 65536)
+        return oaz_set_err(OAZ_ERR_ARG, "set_playout_cap: fast_sims=%d, full_per_65536=%d (>= 0, 0 .. 65536)", fast_sims,
+                           full_per_65536);
+    if (fast_sims > 0) {
+        if (e->cfg.reuse_visits > 0)
+            return oaz_set_err(OAZ_ERR_STATE, "set_playout_cap: the engine was made with reuse_visits=%d (tree reuse)",
+                               e->cfg.reuse_visits);
+        if (e->cfg.leaf_batch > 0)
+            return oaz_set_err(OAZ_ERR_STATE, "set_playout_cap: the engine was made with leaf_batch=%d (no self-play)",
+                               e->cfg.leaf_batch);
+        if (e->cfg.search_time_ns > 0)
+            return oaz_set_err(OAZ_ERR_STATE, "set_playout_cap: the engine has a search-time budget");
+        if (!launch_playout_cap_masks || !launch_selfplay_move_cap)
+            return oaz_set_err(OAZ_ERR_STATE, "set_playout_cap: built without the playout cap kernels");
+        if (!e->pc_flags) {  // its buffers come with the first cap, not at creation
+            OAZ_ON_DEVICE(e->device);
+            if (e->pc_flags.alloc(3 * (size_t)e->G) || e->pc_nrec.alloc(e->G) || e->pc_cnt.alloc(2)) return OAZ_ERR_HIP;
+        }
+    }
+    if (fast_sims == e->pc_fast && (uint32_t)full_per_65536 == e->pc_share) return 0;
+    e->pc_fast = fast_sims;
+    e->pc_share = (uint32_t)full_per_65536;
+    e->selfplay_ready = false;  // the running games end: the next oaz_selfplay_step starts from a reset
+    if (e->pc_cnt) {            // (which also clears these; until then the counters read 0)
+        OAZ_ON_DEVICE(e->device);
+        HIP_TRY(hipMemsetAsync(e->pc_cnt, 0, 2 * sizeof(unsigned long long), e->stream));
+    }
+    return 0;
+}
+
+extern "C" int oaz_selfplay_playout_cap_stats(oaz_engine* e, uint64_t out[2]) {
+    if (!e || !out) return oaz_set_err(OAZ_ERR_ARG, "selfplay_playout_cap_stats: null");
+    out[0] = out[1] = 0;
+    if (e->pc_fast == 0) return 0;
+    OAZ_ON_DEVICE(e->device);
+    HIP_TRY(hipMemcpyAsync(out, e->pc_cnt, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;
 }

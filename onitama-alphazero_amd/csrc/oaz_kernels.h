@@ -176,6 +176,24 @@ __attribute__((weak)) hipError_t launch_selfplay_rebase(const TreeView& t, const
 // two of oaz_selfplay_temperature_stats. Weak for the same reason: such an engine cannot be made without it.
 __attribute__((weak)) hipError_t launch_selfplay_move_temp(const TreeView& t, const SlotView& s, uint32_t temp_plies,
                                                            uint64_t* counters, hipStream_t st);
+// Playout cap randomization (oaz_selfplay_set_playout_cap; oaz_playout_cap.hip): the per-slot
+// state of an engine with a cap, allocated when the cap is set (the engine fills this; all null without a cap).
+struct CapView {
+    uint8_t* full;            // [G] this ply of the slot's game is a full one (playout_cap_full, oaz_device.h)
+    uint8_t* fast;            // [G] phase masks in the form of SlotView::active: 1 = active and a fast ply,
+    uint8_t* fullm;           // [G] 1 = active and a full ply; 0 for every slot that is not playing
+    uint32_t* nrec;           // [G] records of the slot's running game so far (its full plies)
+    unsigned long long* cnt;  // [2] full plies, fast plies played (oaz_selfplay_playout_cap_stats)
+    uint32_t P;               // the full share in 1/65 536
+};
+// Before a capped ply's search: full, fast and fullm of every slot from its game id, ply and active byte.
+// Weak as the launchers above: an engine cannot take a cap in a build without them.
+__attribute__((weak)) hipError_t launch_playout_cap_masks(const SlotView& s, const CapView& c, hipStream_t st);
+// The capped self-play ply, in place of launch_selfplay_move / launch_selfplay_move_temp: the move is played as
+// there (temp_plies = 0: no temperature, counters null), the record is written on a full ply only, at the slot's
+// record count, and a finished game's record count goes into SlotView::fin.
+__attribute__((weak)) hipError_t launch_selfplay_move_cap(const TreeView& t, const SlotView& s, const CapView& c,
+                                                          uint32_t temp_plies, uint64_t* temp_counters, hipStream_t st);
 // Leaf-parallel search (oaz_config.leaf_batch = L > 0; oaz_search_par.hip, DESIGN.md "Leaf-parallel search"): all
 // `sims` playouts of every root in one launch, one workgroup per root, up to L leaves of the root's tree per
 // network pass (virtual loss in oaz_node.pad). The per-root records of a round, allocated by such an engine only

@@ -1459,9 +1459,13 @@ enum TemperatureStat { TS_DRAWS = 0, TS_DIFFER, TS_COUNT };
 // kTemp (oaz_config.temperature_plies = temp_plies > 0, k_selfplay_move_temp): in a game's first temp_plies plies
 // the played move is the child temperature_draw_child draws from the visits instead; the recorded pi is the visit
 // distribution either way. cnt counts the plies that drew and the draws that differ from the most visited child.
-template <bool kTemp>
+// kCap (playout cap randomization, k_selfplay_move_cap in oaz_playout_cap.hip): the move is played as above, but only
+// a full ply (cv.full) writes its record, at the slot's record count cv.nrec instead of at the ply, so a finished
+// game's records are hist[0, nrec) in ply order and fin carries that count (0: a game without a full ply, which
+// k_samples_scan and k_samples_emit pass over); cv.cnt counts the full and the fast plies.
+template <bool kTemp, bool kCap = false>
 __device__ __forceinline__ void selfplay_move_body(const TreeView& t, const SlotView& sv, uint32_t temp_plies,
-                                                   unsigned long long* cnt) {
+                                                   unsigned long long* cnt, const CapView& cv = CapView{}) {
     const uint32_t g = wave_game();
     if (g >= t.G) return;
     const uint8_t act = sv.active[g];
@@ -1481,8 +1485,15 @@ __device__ __forceinline__ void selfplay_move_body(const TreeView& t, const Slot
     float pl;
     int best, K;
     uint32_t mv;
-    const uint32_t hslot = ply < sv.hcap ? ply : sv.hcap - 1;
-    root_pi_best(T, hist[hslot].pi, pl, best, K, mv);
+    bool rec = true;     // this ply writes a record (wave-uniform)
+    uint32_t nrec = ply;  // records of the game before this ply
+    if constexpr (kCap) {
+        rec = cv.full[g] != 0;
+        nrec = cv.nrec[g];
+        if (l == 0) atomicAdd(&cv.cnt[rec ? 0 : 1], 1ull);
+    }
+    const uint32_t hslot = nrec < sv.hcap ? nrec : sv.hcap - 1;
+    root_pi_best(T, rec ? hist[hslot].pi : nullptr, pl, best, K, mv);
     if (kTemp && K > 0 && ply < temp_plies) {  // (wave-uniform)
         uint32_t drawn_mv = 0;
         const int c = root_temperature_child(T, sv.seed, sv.game_id[g], ply, drawn_mv);
@@ -1494,7 +1505,7 @@ __device__ __forceinline__ void selfplay_move_body(const TreeView& t, const Slot
             mv = drawn_mv;
         }
     }
-    if (l == 0) {
+    if (l == 0 && rec) {
         store_state(&hist[hslot].state, s);
         hist[hslot].z = 0.0f;
     }
@@ -1517,8 +1528,10 @@ __device__ __forceinline__ void selfplay_move_body(const TreeView& t, const Slot
     if (over) {
         // the game's records go out after the ply, in slot order (k_samples_scan, k_samples_emit): the
         // history stays until the slot's next game writes its first record in the next ply
-        const uint32_t n = nply < sv.hcap ? nply : sv.hcap;
+        const uint32_t nend = kCap ? nrec + (rec ? 1u : 0u) : nply;
+        const uint32_t n = nend < sv.hcap ? nend : sv.hcap;
         if (l == 0) {
+            if constexpr (kCap) cv.nrec[g] = 0u;
             sv.fin[g] = n | ((uint32_t)res << 24);
             st[GS_FINISHED] += 1;
             if (!is_win(res)) st[GS_CUT] += 1;
@@ -1530,6 +1543,7 @@ __device__ __forceinline__ void selfplay_move_body(const TreeView& t, const Slot
         store_state(&sv.root[g], s);
         sv.ply[g] = nply;
         sv.fin[g] = 0u;
+        if constexpr (kCap) cv.nrec[g] = nrec + (rec ? 1u : 0u);
     }
     // the tree stays as searched (oaz_tree_dump after a ply); the next ply starts from k_tree_reset
 }

@@ -385,6 +385,9 @@ _PROTOS = {
     "oaz_selfplay_step": (C.c_int, [_VOIDP, C.c_int]),
     "oaz_selfplay_stats_get": (C.c_int, [_VOIDP, _P(oaz_selfplay_stats)]),
     "oaz_selfplay_temperature_stats": (C.c_int, [_VOIDP, _P(C.c_uint64 * 2)]),
+    "oaz_playout_cap_full": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "oaz_selfplay_set_playout_cap": (C.c_int, [_VOIDP, C.c_int, C.c_int]),
+    "oaz_selfplay_playout_cap_stats": (C.c_int, [_VOIDP, _P(C.c_uint64 * 2)]),
     "oaz_samples_fetch": (C.c_int, [_VOIDP, _VOIDP, C.c_size_t, _P(C.c_size_t)]),
     "oaz_samples_export_device": (C.c_int, [_VOIDP, _VOIDP, C.c_size_t, _P(C.c_size_t)]),
     "oaz_selfplay_run": (C.c_int, [_VOIDP, C.c_int, _VOIDP, C.c_size_t, _P(C.c_size_t), _P(oaz_selfplay_stats)]),

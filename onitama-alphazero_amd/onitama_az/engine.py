@@ -19,6 +19,14 @@ class SearchResult:
     roots: Optional[np.ndarray] = None  # [G] STATE_DTYPE: the positions searched (Engine.resume only)
 
 
+def playout_cap_full(seed: int, game_id: int, ply: int, full_per_65536: int) -> bool:
+    """The playout cap rule on the host (oaz_playout_cap_full; no device): whether ply `ply` of global game
+    `game_id` under `seed` is a full ply when full_per_65536 of 65 536 plies are."""
+    rc = _abi.load().oaz_playout_cap_full(int(seed), int(game_id), int(ply), int(full_per_65536))
+    _abi.check(rc)
+    return bool(rc)
+
+
 class Engine:
     """One engine on one GPU. Mirrors the state a reference worker thread owns (a model copy
     and its searches, train.rs:218-238) but for `games` games at once."""
@@ -26,6 +34,7 @@ class Engine:
     def __init__(self, config: Optional[_abi.oaz_config] = None, device: int = 0, **overrides):
         lib = _abi.load()
         cfg = config if config is not None else _abi.default_config()
+        playout_cap = overrides.pop("playout_cap", None)  # (fast_sims, full_per_65536): an engine setting, not a field
         for k, v in overrides.items():
             if k == "deck":
                 for i, c in enumerate(v):
@@ -39,6 +48,12 @@ class Engine:
         self._h = C.c_void_p(h)
         self._lib = lib
         self.device = device
+        if playout_cap is not None:
+            try:
+                self.set_playout_cap(*playout_cap)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifecycle --
     def close(self) -> None:
@@ -182,6 +197,20 @@ class Engine:
         selfplay_reset()."""
         out = (C.c_uint64 * 2)()
         _abi.check(self._lib.oaz_selfplay_temperature_stats(self._h, C.byref(out)))
+        return int(out[0]), int(out[1])
+
+    # -- playout cap randomization (Engine(playout_cap=(n, P)): a random share P / 65 536 of the plies is searched with
+    # `sims` playouts and recorded, the others with n playouts and only played) --
+    def set_playout_cap(self, fast_sims: int, full_per_65536: int = 16384) -> None:
+        """The cap for the following self-play (fast_sims = 0: off). Ends the running games: the next
+        selfplay_step() starts from a reset. Refused (OazError) on an engine with tree reuse, leaf batching or a
+        search-time budget."""
+        _abi.check(self._lib.oaz_selfplay_set_playout_cap(self._h, int(fast_sims), int(full_per_65536)))
+
+    def playout_cap_stats(self) -> Tuple[int, int]:
+        """(full plies, fast plies) played since selfplay_reset(); (0, 0) without a cap."""
+        out = (C.c_uint64 * 2)()
+        _abi.check(self._lib.oaz_selfplay_playout_cap_stats(self._h, C.byref(out)))
         return int(out[0]), int(out[1])
 
     # -- self-play --

@@ -57,6 +57,11 @@ class LoopConfig:  # TrainConfig, train.rs:100-154 (defaults of Default::default
     # self-play temperature (oaz_config.temperature_plies): a game's first T plies draw the move in proportion to the
     # root visits; 0 = always the most visited move, as the reference (Q9). The pit and the arena never draw.
     temperature_plies: int = 0
+    # playout cap randomization in self-play (Engine.set_playout_cap): a ply is searched with
+    # mcts_config.max_playouts playouts and recorded with probability playout_cap_full / 65 536, otherwise with
+    # playout_cap_fast_sims playouts and only played. 0 = off: every ply full and recorded, as the reference.
+    playout_cap_fast_sims: int = 0
+    playout_cap_full: int = 16384
     # training on the left-right reflected records too (trainer.train_epochs `reflect`): 0 = off, as the reference;
     # 1 = every drawn sample reflected with probability 1/2; 2 = the buffer together with its reflection (twice
     # the steps per epoch). Self-play, the pit and the arena are not touched.
@@ -135,16 +140,18 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
                       temperature_plies=config.temperature_plies)
             if config.deck is not None:
                 kw.update(fixed_deck=1, deck=config.deck.indices())
+            if config.playout_cap_fast_sims:
+                kw.update(playout_cap=(config.playout_cap_fast_sims, config.playout_cap_full))
             with Engine(device=options.device, **kw) as eng:
                 eng.load_weights(best)
                 if on_replay and world == 1:  # the samples never leave the device
-                    eng.selfplay_run(n_games, cap=0)
+                    _, sp = eng.selfplay_run(n_games, cap=0)
                     n_new = replay.append_engine(eng, it)
                 elif world == 1:
-                    samples, _ = eng.selfplay_run(n_games, cap=n_games * (config.max_plies + 2))
+                    samples, sp = eng.selfplay_run(n_games, cap=n_games * (config.max_plies + 2))
                 else:  # this rank's share, left on the device, then every rank's samples in rank order
                     import torch
-                    eng.selfplay_run(n_games, cap=0)
+                    _, sp = eng.selfplay_run(n_games, cap=0)
                     samples = allgather_samples(eng, world, torch.device("cuda", options.device), comm=comm)
             if on_replay:
                 if world > 1:  # the gathered host array (device to device from the gather: DESIGN.md section 5h)
@@ -157,6 +164,8 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
                     stats.games_played[-1]["unique_records"] = int(n_view)
             else:
                 stats.games_played.append({"games_amnt": n_games, "positions_retrieved": int(len(samples))})
+            if config.playout_cap_fast_sims:  # this rank's plies, full and fast: the records are the full ones
+                stats.games_played[-1]["plies_played"] = int(sp.moves)
             # training epochs (train.rs:257-325)
             if on_replay and world == 1:
                 hist = train_epochs_device(tr, ptr, n_view, epochs=config.training_epochs, batch=config.train_batch_size,
