@@ -997,6 +997,57 @@ int oaz_replay_merge_times(oaz_replay* r, double ms[OAZ_REPLAY_PHASES]);
  * overlap in. */
 int oaz_replay_merge_host(const oaz_sample* in, size_t n, oaz_sample* out, uint32_t* mult, size_t* n_out);
 
+/* ---- held-out evaluation: a split by position and an eval-mode pass -----------------
+ * What lets two training recipes be compared on records neither trained on. Added entries: OAZ_ABI_VERSION
+ * stays 5.
+ *
+ * The split rule. A record is held out as a function of its position only: the key is the replay buffer's (the
+ * 22 bytes kings[2], pawns[2], cards[5], to_move as six little-endian 32-bit words k0 .. k5, the pad bytes 0),
+ * so all copies of a position, in every iteration of a replay window, and a merged record, fall on one side.
+ * With the library's Philox4x32-10 (key; four counter words -> four words w0 .. w3):
+ *   a = philox(seed; k0, k1, k2, k3)
+ *   b = philox(a.w0 | a.w1 << 32; k4, k5, 0x484F4C44 "HOLD", 0)
+ *   held out iff (b.w0 & 0xFFFF) < per_65536, per_65536 in 0 .. 65536 (0: no record, 65536: every record).
+ * pi and z are not looked at. per_65536 > 65536, or a null pointer with n > 0, is OAZ_ERR_ARG; n == 0 is OAZ_OK.
+ * oaz_holdout_pick and oaz_holdout_mask_host need no GPU. oaz_holdout_mask runs a kernel over n records that are
+ * in the memory of `device` (a replay view, oaz_samples_export_device; the caller's writes to them are complete)
+ * and copies the n mask bytes to host_out; the records are only read and do not move. */
+int oaz_holdout_pick(uint64_t seed, const oaz_state* s, uint32_t per_65536); /* 0 / 1; < 0 on bad arguments */
+int oaz_holdout_mask_host(const oaz_sample* in, size_t n, uint64_t seed, uint32_t per_65536, uint8_t* out);
+int oaz_holdout_mask(const oaz_sample* dev, size_t n, uint64_t seed, uint32_t per_65536, int device,
+                     uint8_t* host_out);
+
+/* The eval-mode pass: the trainer's fp32 forward with every BN layer on its running statistics and bn_eps (the
+ * network as the engine plays it), over entries of the trainer's loaded or bound samples. Sums, not means: the
+ * caller divides. */
+typedef struct oaz_eval_stats {
+    uint64_t n;             /* entries evaluated */
+    uint64_t decided;       /* entries with z != 0 */
+    uint64_t top1;          /* entries where pi[argmax p] == max pi (argmax p: the lowest index on ties) */
+    uint64_t sign;          /* decided entries with v * z > 0 */
+    double value_sq;        /* sum (z - v)^2, elementwise (not the training loss's [B,B] broadcast form, which
+                               depends on the batch's composition) */
+    double policy_ce;       /* sum over entries of -sum_k pi_k log p_k; terms with pi_k == 0 contribute 0 */
+    double target_entropy;  /* sum of -sum_k pi_k log pi_k; policy_ce - target_entropy = sum KL(pi || p) */
+    double reserved;        /* 0 */
+} oaz_eval_stats; /* 64 bytes */
+/* idx: n host indices into the samples, NULL = records 0 .. n-1. reflect: n flags with the meaning of
+ * oaz_trainer_set_batches_reflect, NULL = none; predict returns a flagged entry's policy in the reflected
+ * coordinates. Any n >= 0: the call runs chunks of at most max_batch entries, the last one padded to a multiple
+ * of 16 with the padding masked out of every sum and output. An index out of range (or, with idx == NULL,
+ * n above the sample count) or a flag other than 0 / 1 is OAZ_ERR_ARG; no samples loaded or bound is
+ * OAZ_ERR_STATE.
+ * The pass changes nothing a training step reads or reports: parameters, running statistics, momentum buffers,
+ * the gradient buffer, the loss accumulators and the uploaded index matrix stay bit for bit. It runs on the
+ * trainer's stream, after the weight-gradient stream's work, and returns with the stream synchronised.
+ * An entry's outputs depend on that entry alone: predict's p and v of a record are the same bits wherever it
+ * stands in idx, whatever its neighbours and whatever max_batch; evaluate writes a term per entry and adds them
+ * in one fixed order, so its sums are the same bytes for every max_batch.
+ * policy: n x 50 floats (pi's layout), value: n floats. */
+int oaz_trainer_evaluate(oaz_trainer* t, const int32_t* idx, size_t n, const uint8_t* reflect, oaz_eval_stats* out);
+int oaz_trainer_predict(oaz_trainer* t, const int32_t* idx, size_t n, const uint8_t* reflect, float* policy,
+                        float* value);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@
 
 #include <vector>
 
+#include "oaz_holdout_rule.h"
 #include "oaz_host.h"
 #include "oaz_replay_rule.h"
 
@@ -474,5 +475,36 @@ extern "C" int oaz_replay_stats_get(oaz_replay* r, oaz_replay_stats* o) {
 extern "C" int oaz_replay_merge_times(oaz_replay* r, double ms[OAZ_REPLAY_PHASES]) {
     if (!r || !ms) return oaz_set_err(OAZ_ERR_ARG, "replay_merge_times: null");
     for (int k = 0; k < OAZ_REPLAY_PHASES; ++k) ms[k] = r->phase_ms[k];
+    return 0;
+}
+
+// ---- the held-out split over device-resident records (oaz_holdout_rule.h) ----------------------------------
+// One thread per record: its six key words, two Philox blocks, one byte. The records are only read.
+namespace {
+__global__ void __launch_bounds__(kThreads) k_holdout_mask(const uint32_t* rec, size_t n, uint64_t seed, uint32_t per_65536,
+                                                           uint8_t* out) {
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    out[i] = holdout_pick(seed, replay_key(rec + i * kReplaySampleWords), per_65536) ? 1 : 0;
+}
+}  // namespace
+
+extern "C" int oaz_holdout_mask(const oaz_sample* dev, size_t n, uint64_t seed, uint32_t per_65536, int device,
+                                uint8_t* host_out) {
+    if (per_65536 > 65536u) return oaz_set_err(OAZ_ERR_ARG, "holdout_mask: per_65536 %u outside 0 .. 65536", per_65536);
+    if ((!dev || !host_out) && n) return oaz_set_err(OAZ_ERR_ARG, "holdout_mask: null pointer");
+    if (n >= ((size_t)1 << 31)) return oaz_set_err(OAZ_ERR_ARG, "holdout_mask: %zu records (at most 2^31 - 1)", n);
+    if (n == 0) return 0;
+    if (int rc = oaz_check_device("holdout_mask", device)) return rc;
+    OAZ_ON_DEVICE(device);
+    Stream st;  // (declared before the buffer: destroyed, and so waited for, after it is freed by a synchronous hipFree)
+    DevBuf<uint8_t> out;
+    if (int rc = st.create()) return rc;
+    if (int rc = out.alloc(n)) return rc;
+    hipLaunchKernelGGL(k_holdout_mask, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                       reinterpret_cast<const uint32_t*>(dev), n, seed, per_65536, out.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host_out, out, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

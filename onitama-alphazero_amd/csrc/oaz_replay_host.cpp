@@ -1,8 +1,10 @@
 // oaz_replay_host.cpp — oaz_replay_merge_host: the replay buffer's merge rule on the host (include/onitama_az.h,
-// "replay buffer"). No HIP here, so that this file builds and runs alone (tests/c/replay_merge_main.cpp).
+// "replay buffer"), and oaz_holdout_pick / oaz_holdout_mask_host: the held-out split's rule on the host ("held-out
+// evaluation"). No HIP here, so that this file builds and runs alone (tests/c/replay_merge_main.cpp).
 #include <new>
 #include <vector>
 
+#include "oaz_holdout_rule.h"
 #include "oaz_replay_rule.h"
 
 int oaz_set_err(int code, const char* fmt, ...);  // oaz_host.h (which needs the HIP headers)
@@ -61,5 +63,25 @@ extern "C" int oaz_replay_merge_host(const oaz_sample* in, size_t n, oaz_sample*
     } catch (const std::bad_alloc&) {
         return oaz_set_err(OAZ_ERR_CAPACITY, "replay_merge_host: out of host memory for %zu records", n);
     }
+    return 0;
+}
+
+// ---- the held-out split on the host (oaz_holdout_rule.h) ---------------------------------------------------
+static bool holdout_of(uint64_t seed, const void* state, uint32_t per_65536) {
+    uint32_t w[kReplayKeyWords];
+    memcpy(w, state, sizeof(w));
+    return holdout_pick(seed, replay_key(w), per_65536);
+}
+
+extern "C" int oaz_holdout_pick(uint64_t seed, const oaz_state* s, uint32_t per_65536) {
+    if (!s) return oaz_set_err(OAZ_ERR_ARG, "holdout_pick: null state");
+    if (per_65536 > 65536u) return oaz_set_err(OAZ_ERR_ARG, "holdout_pick: per_65536 %u outside 0 .. 65536", per_65536);
+    return holdout_of(seed, s, per_65536) ? 1 : 0;
+}
+
+extern "C" int oaz_holdout_mask_host(const oaz_sample* in, size_t n, uint64_t seed, uint32_t per_65536, uint8_t* out) {
+    if (per_65536 > 65536u) return oaz_set_err(OAZ_ERR_ARG, "holdout_mask_host: per_65536 %u outside 0 .. 65536", per_65536);
+    if ((!in || !out) && n) return oaz_set_err(OAZ_ERR_ARG, "holdout_mask_host: null pointer");
+    for (size_t i = 0; i < n; ++i) out[i] = holdout_of(seed, &in[i], per_65536) ? 1 : 0;
     return 0;
 }

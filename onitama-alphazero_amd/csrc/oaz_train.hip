@@ -28,7 +28,9 @@
 //                    k_conv<DGRAD>   not for the first conv: the same conv kernel on flipped/transposed weights,
 //                                    epilogue = skip add + ReLU mask + BN-backward partial sums of the layer below
 //   apply:           k_sgd           (+ the packed conv weights of the next step)
-// k_pack (set_weights) and k_bn_stats_io (data-parallel epoch end) are outside the step.
+// k_pack (set_weights) and k_bn_stats_io (data-parallel epoch end) are outside the step, and so is the eval-mode
+// pass (oaz_trainer_evaluate / predict: k_gather, k_conv<FWD>, k_bn_act_eval, k_head_conv, k_head_eval, then
+// k_eval_tiles -> k_eval_total), which writes nothing a step reads.
 // All reductions are two-stage with fixed order (deterministic; no float atomics).
 #include <hip/hip_runtime.h>
 
@@ -954,6 +956,182 @@ __global__ void k_pack(const float* W, int cin, int chunks, float4* wf, float4* 
     if (wd) wd[id] = make_float4(d[0], d[1], d[2], d[3]);
 }
 
+// ---- the eval-mode pass (oaz_trainer_evaluate / oaz_trainer_predict) ----------------
+// The forward with every BN on its running statistics: k_gather, then per conv k_conv<FWD> (its BN partial
+// sums are written and not read) and k_bn_act_eval, then k_head_conv (its partials likewise) and k_head_eval.
+// Nothing here reduces over the batch, so a record's outputs depend on that record alone: k_conv accumulates
+// each (square, sample, channel) over the taps and channel chunks in an order without B in it.
+
+// A = relu((Z - running_mean) / sqrt(running_var + eps) * gamma + beta [+ skip]): k_bn_act_cfin's apply on the
+// running statistics, which are only read.
+__global__ __launch_bounds__(256) void k_bn_act_eval(const float* rmean, const float* rvar, float eps, const float* Z,
+                                                     const float* gamma, const float* beta, const float* skip, float* A,
+                                                     long long n) {
+    __shared__ float cf[4][64];  // mean, invstd, gamma, beta
+    if (threadIdx.x < 64) {
+        const int c = threadIdx.x;
+        cf[0][c] = rmean[c];
+        cf[1][c] = (float)(1.0 / sqrt((double)rvar[c] + (double)eps));
+        cf[2][c] = gamma[c];
+        cf[3][c] = beta[c];
+    }
+    __syncthreads();
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t * 4 < n; t += (long long)gridDim.x * blockDim.x) {
+        const int c0 = (int)((t * 4) & 63);
+        const float4 z = reinterpret_cast<const float4*>(Z)[t];
+        float v[4] = {z.x, z.y, z.z, z.w};
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (skip) s = reinterpret_cast<const float4*>(skip)[t];
+        const float sk[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float y = (v[k] - cf[0][c0 + k]) * cf[1][c0 + k] * cf[2][c0 + k] + cf[3][c0 + k];
+            if (skip) y += sk[k];
+            v[k] = y > 0.0f ? y : 0.0f;
+        }
+        reinterpret_cast<float4*>(A)[t] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// A record's terms of oaz_eval_stats: the three sums' addends and the flag bits.
+struct EvalTerm {
+    double value_sq, policy_ce, target_entropy;
+    unsigned long long flags;
+};
+enum { EVAL_DECIDED = 1, EVAL_TOP1 = 2, EVAL_SIGN = 4 };
+static_assert(kTPS == 64, "k_head_eval: one wave per sample, one policy entry per lane");
+
+__device__ __forceinline__ double sumTd(double v) {
+#pragma unroll
+    for (int o = 1; o < kTPS; o <<= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Head BN on the running statistics, the value MLP (tanh), the policy linear + softmax: k_head_sample's forward
+// in its order of operations, one wave per sample, the first `valid` of the B samples (the rest is padding
+// and writes nothing). terms (or null): the sample's EvalTerm, from the float logits in double:
+// log p_k = (l_k - max l) - log(sum exp(l - max l)). pol / val (or null): p [50] and v.
+__global__ __launch_bounds__(256) void k_head_eval(const float* hz, const float* P, HeadOff o, float eps, const float* pi,
+                                                   const float* z, int B, int valid, EvalTerm* terms, float* pol,
+                                                   float* val) {
+    __shared__ float W[kHeadW];  // l1w[64][25] l1b[64] l2w[64] l2b | plw[50][50] plb[50]
+    __shared__ float hv[kHS][25], hp[kHS][50];
+    const int tid = threadIdx.x, j = tid % kTPS, sl = tid / kTPS;
+    for (int k = tid; k < kHeadVW; k += 256) W[k] = P[o.l1w + k];
+    for (int k = tid; k < 2550; k += 256) W[kHeadVW + k] = P[o.plw + k];
+    const float* l1w = W;
+    const float* l1b = W + 1600;
+    const float* l2w = W + 1664;
+    const float* plw = W + kHeadVW;
+    const float* plb = plw + 2500;
+    const int b = blockIdx.x * kHS + sl;
+    const bool ok = b < valid;
+    if (j < 25) {
+        const float vm = P[o.vrm], vi = (float)(1.0 / sqrt((double)P[o.vrv] + (double)eps));
+        float y = 0.0f;
+        if (ok) y = (hz[(size_t)(j * B + b) * 4] - vm) * vi * P[o.vg] + P[o.vb];
+        hv[sl][j] = y > 0.0f ? y : 0.0f;
+    }
+    if (j < 50) {
+        const int c = j / 25, sq = j % 25;
+        const float pm = P[o.prm + c], pv = (float)(1.0 / sqrt((double)P[o.prv + c] + (double)eps));
+        float y = 0.0f;
+        if (ok) y = (hz[(size_t)(sq * B + b) * 4 + 1 + c] - pm) * pv * P[o.pg + c] + P[o.pb + c];
+        hp[sl][j] = y > 0.0f ? y : 0.0f;
+    }
+    __syncthreads();
+    const float l2b = W[1728];
+    float a = l1b[j];
+    for (int sq = 0; sq < 25; ++sq) a += l1w[j * 25 + sq] * hv[sl][sq];
+    a = a > 0.0f ? a : 0.0f;
+    const float v = tanhf(sumT(l2w[j] * a) + l2b);
+    const bool in = j < 50;
+    float lg = -INFINITY;
+    if (in) {
+        lg = plb[j];
+        for (int k = 0; k < 50; ++k) lg += plw[j * 50 + k] * hp[sl][k];
+    }
+    const float mxl = maxT(lg);
+    const float e = in ? expf(lg - mxl) : 0.0f;
+    const float se = sumT(e);
+    const float p = e / se;
+    if (!ok) return;  // (a whole wave: no shuffle below is left without its partners)
+    if (pol && in) pol[(size_t)b * 50 + j] = p;
+    if (val && j == 0) val[b] = v;
+    if (!terms) return;
+    const float t = in ? pi[(size_t)b * 50 + j] : 0.0f;
+    // arg-max of p, the lowest index on ties, and the target there against the largest target
+    float bp = in ? p : -1.0f;
+    int bj = j;
+#pragma unroll
+    for (int s = 1; s < kTPS; s <<= 1) {
+        const float op = __shfl_xor(bp, s);
+        const int oj = __shfl_xor(bj, s);
+        if (op > bp || (op == bp && oj < bj)) {
+            bp = op;
+            bj = oj;
+        }
+    }
+    const float t_at = __shfl(t, bj), t_max = maxT(in ? t : -INFINITY);
+    double ce = 0.0, ent = 0.0;
+    if (in && t != 0.0f) {
+        ce = -(double)t * ((double)(lg - mxl) - log((double)se));
+        ent = -(double)t * log((double)t);
+    }
+    ce = sumTd(ce);
+    ent = sumTd(ent);
+    if (j == 0) {
+        const float zz = z[b];
+        const double d = (double)zz - (double)v;
+        unsigned long long f = 0;
+        if (zz != 0.0f) f |= EVAL_DECIDED;
+        if (t_at == t_max) f |= EVAL_TOP1;
+        if (zz != 0.0f && v * zz > 0.0f) f |= EVAL_SIGN;
+        terms[b] = EvalTerm{d * d, ce, ent, f};
+    }
+}
+
+// The sum of the terms in one fixed order, whatever chunks wrote them: a workgroup per tile of kEvalTile records
+// (thread t adds records t, t + 256, ... of its tile in that order, then a pairwise fold over the threads in
+// LDS), then one workgroup over the tiles' sums in the same way.
+constexpr int kEvalTile = 1024;
+__device__ __forceinline__ void eval_add(oaz_eval_stats& a, const oaz_eval_stats& b) {
+    a.n += b.n, a.decided += b.decided, a.top1 += b.top1, a.sign += b.sign;
+    a.value_sq += b.value_sq, a.policy_ce += b.policy_ce, a.target_entropy += b.target_entropy;
+}
+__device__ __forceinline__ oaz_eval_stats eval_fold(oaz_eval_stats s, oaz_eval_stats* sh) {  // [256]; all threads call
+    const int t = threadIdx.x;
+    sh[t] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) eval_add(sh[t], sh[t + w]);
+        __syncthreads();
+    }
+    return sh[0];
+}
+__global__ __launch_bounds__(256) void k_eval_tiles(const EvalTerm* terms, long long n, oaz_eval_stats* part) {
+    __shared__ oaz_eval_stats sh[256];
+    oaz_eval_stats s{};
+    const long long r0 = (long long)blockIdx.x * kEvalTile;
+    for (int u = threadIdx.x; u < kEvalTile && r0 + u < n; u += 256) {
+        const EvalTerm e = terms[r0 + u];
+        oaz_eval_stats one{};
+        one.n = 1, one.decided = e.flags & EVAL_DECIDED ? 1 : 0, one.top1 = e.flags & EVAL_TOP1 ? 1 : 0;
+        one.sign = e.flags & EVAL_SIGN ? 1 : 0;
+        one.value_sq = e.value_sq, one.policy_ce = e.policy_ce, one.target_entropy = e.target_entropy;
+        eval_add(s, one);
+    }
+    s = eval_fold(s, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void k_eval_total(const oaz_eval_stats* part, int nparts, oaz_eval_stats* out) {
+    __shared__ oaz_eval_stats sh[256];
+    oaz_eval_stats s{};
+    for (int w = threadIdx.x; w < nparts; w += 256) eval_add(s, part[w]);
+    s = eval_fold(s, sh);
+    if (threadIdx.x == 0) *out = s;
+}
+
 }  // namespace tr
 
 using namespace tr;
@@ -998,6 +1176,12 @@ struct oaz_trainer {
     DevBuf<int32_t> idx;  // grow-only
     int n_batches = 0, batch = 0;
     DevBuf<double> loss_acc;
+    // the eval-mode pass (grow-only, made by its first call): its own index entries, the per-record terms and
+    // their tile sums, predict's outputs
+    DevBuf<int32_t> eval_idx;
+    DevBuf<EvalTerm> eval_terms;
+    DevBuf<oaz_eval_stats> eval_part, eval_sum;
+    DevBuf<float> eval_pol, eval_val;
     Event ev_dz[2], ev_w[2], ev_h[2], ev_done;  // (after the buffers: destroyed before them)
 
     // `count` elements and a 16-byte pad, zero-filled on the trainer's stream: ordered before its work (create syncs)
@@ -1488,6 +1672,106 @@ extern "C" int oaz_trainer_losses(oaz_trainer* t, double out[3]) {
 extern "C" int oaz_trainer_sync(oaz_trainer* t) {
     if (!t) return oaz_set_err(OAZ_ERR_ARG, "trainer: null");
     OAZ_ON_DEVICE(t->device);
+    HIP_TRY(hipStreamSynchronize(t->st));
+    return 0;
+}
+
+// ---- the eval-mode pass: oaz_trainer_evaluate / oaz_trainer_predict ------------------------------------------
+// n entries (idx, or records 0 .. n-1; reflect flags as oaz_trainer_set_batches_reflect) in chunks of at most
+// max_batch, the last one padded to a multiple of 16 with a valid index and masked by `valid`. Writes the step's
+// activations and partial-sum buffers and its own buffers only: parameters, running statistics, momenta,
+// gradients, loss accumulators and the uploaded index matrix stay as they are. want_terms: the per-record terms
+// into eval_terms; else p and v into eval_pol / eval_val.
+static int eval_pass(oaz_trainer* t, const int32_t* idx, size_t n, const uint8_t* reflect, bool want_terms, const char* who) {
+    if (!t->samples) return oaz_set_err(OAZ_ERR_STATE, "%s: no samples loaded or bound", who);
+    if (n >= ((size_t)1 << 31)) return oaz_set_err(OAZ_ERR_ARG, "%s: %zu entries (at most 2^31 - 1)", who, n);
+    if (!idx && n > t->n_samples) return oaz_set_err(OAZ_ERR_ARG, "%s: %zu entries of %zu samples", who, n, t->n_samples);
+    for (size_t i = 0; idx && i < n; ++i)
+        if (idx[i] < 0 || (size_t)idx[i] >= t->n_samples)
+            return oaz_set_err(OAZ_ERR_ARG, "%s: index %d out of range (%zu samples)", who, idx[i], t->n_samples);
+    for (size_t i = 0; reflect && i < n; ++i)
+        if (reflect[i] > 1) return oaz_set_err(OAZ_ERR_ARG, "%s: reflect flag %d of entry %zu is not 0 or 1", who, reflect[i], i);
+    if (n == 0) return 0;
+    const size_t npad = (n + 15) / 16 * 16;
+    std::vector<int32_t> ent(npad);
+    for (size_t i = 0; i < n; ++i)
+        ent[i] = (int32_t)((uint32_t)(idx ? idx[i] : (int32_t)i) | (reflect && reflect[i] ? kGatherReflect : 0u));
+    for (size_t i = n; i < npad; ++i) ent[i] = ent[0] & (int32_t)~kGatherReflect;
+    hipStream_t st = t->st;
+    const bool grow = npad > t->eval_idx.size() || (want_terms ? n > t->eval_terms.size() : n > t->eval_val.size());
+    if (grow) HIP_TRY(hipStreamSynchronize(st));  // old buffers are freed: after the work that reads them
+    if (int rc = t->eval_idx.reserve(npad)) return rc;
+    if (want_terms) {
+        if (int rc = t->eval_terms.reserve(n)) return rc;
+        if (int rc = t->eval_part.reserve((n + kEvalTile - 1) / kEvalTile)) return rc;
+        if (int rc = t->eval_sum.reserve(1)) return rc;
+    } else {
+        if (int rc = t->eval_pol.reserve(n * 50)) return rc;
+        if (int rc = t->eval_val.reserve(n)) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(t->eval_idx, ent.data(), npad * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    // the weight-gradient stream may still read the activations and partials of the last step
+    HIP_TRY(hipEventRecord(t->ev_done, t->st2));
+    HIP_TRY(hipStreamWaitEvent(st, t->ev_done, 0));
+    const float eps = (float)t->cfg.bn_eps;
+    float* P = t->P;
+    constexpr int rows_wg = 16 * kConvRG;
+    for (size_t off = 0; off < npad; off += (size_t)t->maxB) {
+        const int B = (int)(npad - off < (size_t)t->maxB ? npad - off : (size_t)t->maxB), R = B * 25;
+        const int valid = (int)(n - off < (size_t)B ? n - off : (size_t)B);
+        hipLaunchKernelGGL(k_gather, dim3((R + 51 * B + 255) / 256), dim3(256), 0, st, t->samples, t->eval_idx + off, 0, B,
+                           t->X0, t->pi, t->z);
+        const long long nel = (long long)R * kC;
+        for (int l = 0; l < t->nconv; ++l) {
+            const wl::ConvBn& cv = t->L.tower[l];
+            ConvArgs a{};
+            a.in = l == 0 ? t->X0 : t->A[l - 1];
+            a.w = t->wf[l];
+            a.bias = P + cv.b;
+            a.out = t->Z[l];
+            a.part = t->part;
+            a.chunks = l == 0 ? 2 : 4;
+            a.B = B;
+            launch_conv<CONV_FWD>(l == 0 ? 2 : 4, dim3((B + rows_wg - 1) / rows_wg, 25), st, a);
+            const float* skip = (l >= 2 && l % 2 == 0) ? t->A[l - 2] : nullptr;
+            hipLaunchKernelGGL(k_bn_act_eval, dim3((unsigned)((nel / 4 + 255) / 256)), dim3(256), 0, st, P + cv.mean,
+                               P + cv.var, eps, t->Z[l], P + cv.gamma, P + cv.beta, skip, t->A[l], nel);
+        }
+        hipLaunchKernelGGL(k_head_conv, dim3((R + 255) / 256), dim3(256), 0, st, t->A[t->nconv - 1], P, t->h, t->hz,
+                           t->hpart, R);
+        hipLaunchKernelGGL(k_head_eval, dim3((B + kHS - 1) / kHS), dim3(256), 0, st, t->hz, P, t->h, eps, t->pi, t->z, B,
+                           valid, want_terms ? t->eval_terms + off : nullptr, want_terms ? nullptr : t->eval_pol + off * 50,
+                           want_terms ? nullptr : t->eval_val + off);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));  // `ent` was read
+    return 0;
+}
+
+extern "C" int oaz_trainer_evaluate(oaz_trainer* t, const int32_t* idx, size_t n, const uint8_t* reflect,
+                                    oaz_eval_stats* out) {
+    if (!t || !out) return oaz_set_err(OAZ_ERR_ARG, "trainer_evaluate: null");
+    OAZ_ON_DEVICE(t->device);
+    if (int rc = eval_pass(t, idx, n, reflect, true, "trainer_evaluate")) return rc;
+    memset(out, 0, sizeof(*out));
+    if (n == 0) return 0;
+    const int tiles = (int)((n + kEvalTile - 1) / kEvalTile);
+    hipLaunchKernelGGL(k_eval_tiles, dim3(tiles), dim3(256), 0, t->st, t->eval_terms, (long long)n, t->eval_part);
+    hipLaunchKernelGGL(k_eval_total, dim3(1), dim3(256), 0, t->st, t->eval_part, tiles, t->eval_sum);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, t->eval_sum, sizeof(*out), hipMemcpyDeviceToHost, t->st));
+    HIP_TRY(hipStreamSynchronize(t->st));
+    return 0;
+}
+
+extern "C" int oaz_trainer_predict(oaz_trainer* t, const int32_t* idx, size_t n, const uint8_t* reflect, float* policy,
+                                   float* value) {
+    if (!t || ((!policy || !value) && n)) return oaz_set_err(OAZ_ERR_ARG, "trainer_predict: null");
+    OAZ_ON_DEVICE(t->device);
+    if (int rc = eval_pass(t, idx, n, reflect, false, "trainer_predict")) return rc;
+    if (n == 0) return 0;
+    HIP_TRY(hipMemcpyAsync(policy, t->eval_pol, n * 50 * sizeof(float), hipMemcpyDeviceToHost, t->st));
+    HIP_TRY(hipMemcpyAsync(value, t->eval_val, n * sizeof(float), hipMemcpyDeviceToHost, t->st));
     HIP_TRY(hipStreamSynchronize(t->st));
     return 0;
 }

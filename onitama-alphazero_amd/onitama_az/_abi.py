@@ -300,6 +300,14 @@ class oaz_replay_stats(C.Structure):  # 56 bytes
 
 REPLAY_PHASES = ("key", "insert", "lookup", "scan", "group", "emit")  # oaz_replay_merge_times
 
+
+class oaz_eval_stats(C.Structure):  # 64 bytes: sums over the evaluated entries (oaz_trainer_evaluate)
+    _fields_ = ([(k, C.c_uint64) for k in ("n", "decided", "top1", "sign")] +
+                [(k, C.c_double) for k in ("value_sq", "policy_ce", "target_entropy", "reserved")])
+
+
+assert C.sizeof(oaz_eval_stats) == 64
+
 assert C.sizeof(oaz_state) == 24
 assert C.sizeof(oaz_move) == 4
 assert C.sizeof(oaz_node) == 32
@@ -462,6 +470,11 @@ _PROTOS = {
     "oaz_replay_stats_get": (C.c_int, [_VOIDP, _P(oaz_replay_stats)]),
     "oaz_replay_merge_times": (C.c_int, [_VOIDP, _P(C.c_double * 6)]),
     "oaz_replay_merge_host": (C.c_int, [_VOIDP, C.c_size_t, _VOIDP, _VOIDP, _P(C.c_size_t)]),
+    "oaz_holdout_pick": (C.c_int, [C.c_uint64, _VOIDP, C.c_uint32]),
+    "oaz_holdout_mask_host": (C.c_int, [_VOIDP, C.c_size_t, C.c_uint64, C.c_uint32, _VOIDP]),
+    "oaz_holdout_mask": (C.c_int, [_VOIDP, C.c_size_t, C.c_uint64, C.c_uint32, C.c_int, _VOIDP]),
+    "oaz_trainer_evaluate": (C.c_int, [_VOIDP, _VOIDP, C.c_size_t, _VOIDP, _P(oaz_eval_stats)]),
+    "oaz_trainer_predict": (C.c_int, [_VOIDP, _VOIDP, C.c_size_t, _VOIDP, _VOIDP, _VOIDP]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -24,7 +24,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import _abi
+from . import _abi, holdout
 from .engine import Engine
 from .evaluator import EvaluatorConfig, Evaluator, PitStatistics
 from .game import Deck
@@ -73,6 +73,14 @@ class LoopConfig:  # TrainConfig, train.rs:100-154 (defaults of Default::default
     replay_iterations: int = 1  # train on the last N iterations' samples (capped by buffer_size)
     merge_duplicates: bool = False  # records of equal position become one, with the mean pi and the mean z
     device_replay: bool = False  # the replay path with a window of one and without merging: the same training
+    # held-out evaluation (onitama_az.holdout, Trainer.evaluate). Either option set: the
+    # records whose position the split rule picks (share holdout_per_65536 / 65 536, keyed by `seed` in every
+    # iteration, so a position never changes sides inside a replay window) are never trained on, and rank 0
+    # evaluates them in eval mode before and after the iteration's epochs (Stats.evaluation); holdout_per_65536
+    # == 0 with evaluate: nothing is held out and all records are evaluated. Both at their defaults: the loop
+    # launches and draws what it did.
+    holdout_per_65536: int = 0
+    evaluate: bool = False
 
 
 @dataclass
@@ -84,6 +92,8 @@ class Stats:  # stats.rs:7-24
     was_best_change: List[bool] = field(default_factory=list)
     fight_statistics: List[PitStatistics] = field(default_factory=list)
     games_played: List[dict] = field(default_factory=list)
+    # per iteration {"records", "held_out", "before": {...}, "after": {...}} (EvalStats.summary); empty when off
+    evaluation: List[dict] = field(default_factory=list)
 
     def save(self, path: str) -> None:
         with open(path, "w") as f:
@@ -123,6 +133,7 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
     n_games = config.self_play_game_amnt * config.thread_amnt
     mc = config.mcts_config
     on_replay = config.replay_iterations != 1 or config.merge_duplicates or config.device_replay
+    on_eval = bool(config.holdout_per_65536) or config.evaluate
     own_replay = None
     if on_replay and replay is None:
         replay = own_replay = ReplayBuffer(capacity=config.buffer_size, window=config.replay_iterations,
@@ -166,21 +177,42 @@ def train(config: LoopConfig, folder: Optional[str] = None, options: Options = N
                 stats.games_played.append({"games_amnt": n_games, "positions_retrieved": int(len(samples))})
             if config.playout_cap_fast_sims:  # this rank's plies, full and fast: the records are the full ones
                 stats.games_played[-1]["plies_played"] = int(sp.moves)
+            # the held-out split and the evaluation before the epochs (every rank computes the same split)
+            sub = held = before = None
+            if on_eval:
+                if config.holdout_per_65536:
+                    m = holdout.mask((ptr, n_view) if on_replay else samples, config.seed, config.holdout_per_65536,
+                                     device=options.device)
+                    sub, held = holdout.split(m)
+                stats.games_played[-1]["held_out"] = 0 if held is None else int(len(held))
+                if rank == 0:
+                    if on_replay:
+                        tr.bind_device_samples(ptr, n_view)
+                    else:
+                        tr.load_samples(samples)
+                    before = tr.evaluate(held).summary()
+            kw_sub = {} if sub is None else {"subset": sub}
             # training epochs (train.rs:257-325)
             if on_replay and world == 1:
                 hist = train_epochs_device(tr, ptr, n_view, epochs=config.training_epochs, batch=config.train_batch_size,
-                                           seed=config.seed + 1000 + it, reflect=config.reflect_augment)
+                                           seed=config.seed + 1000 + it, reflect=config.reflect_augment, **kw_sub)
             elif on_replay:
                 hist = train_epochs_dp_device(tr, ptr, n_view, epochs=config.training_epochs,
                                               batch=config.train_batch_size, seed=config.seed + 1000 + it, rank=rank,
-                                              world=world, comm=comm, reflect=config.reflect_augment)
+                                              world=world, comm=comm, reflect=config.reflect_augment, **kw_sub)
             elif world == 1:
                 hist = train_epochs(tr, samples, epochs=config.training_epochs, batch=config.train_batch_size,
-                                    seed=config.seed + 1000 + it, reflect=config.reflect_augment)
+                                    seed=config.seed + 1000 + it, reflect=config.reflect_augment, **kw_sub)
             else:
                 hist = train_epochs_dp(tr, samples, epochs=config.training_epochs, batch=config.train_batch_size,
                                        seed=config.seed + 1000 + it, rank=rank, world=world, comm=comm,
-                                       reflect=config.reflect_augment)
+                                       reflect=config.reflect_augment, **kw_sub)
+            if on_eval:  # the same records after the epochs; rank 0's numbers on every rank
+                after = tr.evaluate(held).summary() if rank == 0 else None
+                before, after = _bcast((before, after), world)
+                stats.evaluation.append({"iteration": it, "records": int(after["n"]),
+                                         "held_out": 0 if held is None else int(len(held)), "before": before,
+                                         "after": after})
             if config.reflect_augment:  # the samples the epochs drew, reflected ones included
                 stats.games_played[-1]["positions_trained"] = sum(h.steps for h in hist) * config.train_batch_size
             k = max(1, len(hist))

@@ -31,6 +31,53 @@ class EpochLoss:  # the per-epoch line of train.rs:316-324
     steps: int
 
 
+@dataclass
+class EvalStats:
+    """oaz_eval_stats: sums over the entries of one Trainer.evaluate call (the network in eval mode, every BN on its
+    running statistics), and the means a reader wants of them. All means are 0.0 over no entries."""
+    n: int = 0
+    decided: int = 0  # entries with z != 0
+    top1: int = 0  # entries whose arg-max prior is a largest entry of pi
+    sign: int = 0  # decided entries with v z > 0
+    value_sq_sum: float = 0.0  # sum (z - v)^2, elementwise
+    policy_ce_sum: float = 0.0  # sum of -sum_k pi_k log p_k
+    target_entropy_sum: float = 0.0  # sum of -sum_k pi_k log pi_k
+
+    def _per(self, x: float, d: float) -> float:
+        return x / d if d else 0.0
+
+    @property
+    def value_mse(self) -> float:
+        return self._per(self.value_sq_sum, self.n)
+
+    @property
+    def policy_ce(self) -> float:
+        return self._per(self.policy_ce_sum, self.n)
+
+    @property
+    def policy_kl(self) -> float:
+        return self._per(self.policy_ce_sum - self.target_entropy_sum, self.n)
+
+    @property
+    def top1_rate(self) -> float:
+        return self._per(self.top1, self.n)
+
+    @property
+    def sign_rate(self) -> float:
+        return self._per(self.sign, self.decided)
+
+    @property
+    def policy_loss(self) -> float:
+        """policy_ce_sum / (25 n): the unit of EpochLoss.policy (alphaloss's mean over B x 25 entries)."""
+        return self._per(self.policy_ce_sum, 25 * self.n)
+
+    def summary(self) -> dict:
+        """The counts and the means as one JSON-ready dict (Stats.evaluation)."""
+        return {"n": self.n, "decided": self.decided, "value_mse": self.value_mse, "policy_ce": self.policy_ce,
+                "policy_kl": self.policy_kl, "policy_loss": self.policy_loss, "top1_rate": self.top1_rate,
+                "sign_rate": self.sign_rate}
+
+
 class Trainer:
     def __init__(self, blocks: int, max_batch: int = 512, learning_rate: float = 5e-3, momentum: float = 0.9,
                  weight_decay: float = 1e-4, value_loss_broadcast: bool = True, device: int = 0,
@@ -51,6 +98,7 @@ class Trainer:
         self._h, self._lib, self.config, self.device = C.c_void_p(h), lib, cfg, device
         self.blocks = int(blocks)
         self.n_params = int(lib.oaz_weight_count(self.blocks, 64, 21))
+        self.n_samples = 0
 
     def close(self) -> None:
         if self._h:
@@ -142,6 +190,41 @@ class Trainer:
     def sync(self) -> None:
         self._check(self._lib.oaz_trainer_sync(self._h))
 
+    # -- the eval-mode pass ------------------------------------------------------------------------
+    def _entries(self, idx, reflect):
+        """(idx int32 or None, n, reflect uint8 or None) of evaluate / predict: idx None = every sample."""
+        if idx is None:
+            n = int(self.n_samples)
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+            n = len(idx)
+        if reflect is not None:
+            reflect = np.ascontiguousarray(reflect, dtype=np.uint8).reshape(-1)
+            assert len(reflect) == n
+        return idx, n, reflect
+
+    def evaluate(self, idx: Optional[np.ndarray] = None, reflect: Optional[np.ndarray] = None) -> EvalStats:
+        """The network in eval mode (every BN on its running statistics) over samples[idx] (None: all of the loaded
+        or bound samples); reflect: a flag per entry, as set_batches'. oaz_trainer_evaluate: nothing a training step
+        reads or reports changes, and the sums are the same bytes for every max_batch."""
+        idx, n, reflect = self._entries(idx, reflect)
+        st = _abi.oaz_eval_stats()
+        self._check(self._lib.oaz_trainer_evaluate(self._h, None if idx is None else _abi.ptr(idx), n,
+                                                   None if reflect is None else _abi.ptr(reflect), C.byref(st)))
+        return EvalStats(int(st.n), int(st.decided), int(st.top1), int(st.sign), float(st.value_sq),
+                         float(st.policy_ce), float(st.target_entropy))
+
+    def predict(self, idx: Optional[np.ndarray] = None,
+                reflect: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(p [n, 50], v [n]) float32 of the same pass (oaz_trainer_predict); a flagged entry's p is in the
+        reflected coordinates."""
+        idx, n, reflect = self._entries(idx, reflect)
+        p, v = np.zeros((n, 50), dtype=np.float32), np.zeros(n, dtype=np.float32)
+        self._check(self._lib.oaz_trainer_predict(self._h, None if idx is None else _abi.ptr(idx), n,
+                                                  None if reflect is None else _abi.ptr(reflect), _abi.ptr(p),
+                                                  _abi.ptr(v)))
+        return p, v
+
 
 def choose_batches(rng: np.random.Generator, n_samples: int, batch: int, n_batches: int) -> np.ndarray:
     """`data_buffer.iter().choose_multiple(&mut rng, batch)` per batch (train.rs:272-276): a uniform
@@ -167,7 +250,8 @@ def choose_batches_doubled(rng: np.random.Generator, n_samples: int, batch: int,
 
 
 def epoch_batches(rng: np.random.Generator, flag_rng: np.random.Generator, n_samples: int, batch: int,
-                  reflect: int, rank: int = 0, world: int = 1) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+                  reflect: int, rank: int = 0, world: int = 1,
+                  subset: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
     """One epoch's (index matrix, flag matrix or None) for `reflect` (train_epochs). rng is the index generator and
     flag_rng the flags' own: mode 0 and 1 draw from rng exactly what the loop without the feature draws. world > 1
     (train_epochs_dp): every rank draws the whole matrices and gets its batch / world columns of both."""
@@ -178,8 +262,20 @@ def epoch_batches(rng: np.random.Generator, flag_rng: np.random.Generator, n_sam
     else:
         idx = choose_batches(rng, n_samples, batch, n_samples // batch)
         flags = choose_reflect(flag_rng, idx.shape) if reflect == 1 else None
+    if subset is not None:
+        idx = subset[idx]
     cols = slice(rank * (batch // world), (rank + 1) * (batch // world))
     return idx[:, cols], (None if flags is None else flags[:, cols])
+
+
+def _subset(subset, n_samples: int) -> Tuple[Optional[np.ndarray], int]:
+    """(the subset as int32 or None, the number of entries an epoch draws from)."""
+    if subset is None:
+        return None, int(n_samples)
+    subset = np.ascontiguousarray(subset, dtype=np.int32).reshape(-1)
+    if len(subset) and (subset.min() < 0 or subset.max() >= n_samples):
+        raise ValueError("subset: an index outside the samples")
+    return subset, len(subset)
 
 
 def _set_batches(trainer, idx, flags) -> None:
@@ -190,7 +286,7 @@ def _set_batches(trainer, idx, flags) -> None:
 
 
 def train_epochs(trainer: Trainer, samples: np.ndarray, epochs: int = 10, batch: int = 512,
-                 seed: int = 0, reflect: int = 0) -> List[EpochLoss]:
+                 seed: int = 0, reflect: int = 0, subset: Optional[np.ndarray] = None) -> List[EpochLoss]:
     """The epoch loop of train.rs:264-325 on one GPU (stops early, as the reference, when the
     buffer holds fewer than `batch` samples).
 
@@ -198,30 +294,37 @@ def train_epochs(trainer: Trainer, samples: np.ndarray, epochs: int = 10, batch:
     reference does not). 0 = off: the index stream of a seed is what it always was. 1 = every drawn entry is
     reflected with probability 1/2, the flags from a generator of their own (seed and REFLECT_TAG), the index
     stream and the epoch length unchanged. 2 = the buffer together with its reflection: every batch a draw
-    without replacement from the 2 n entries, 2 n // batch batches per epoch."""
+    without replacement from the 2 n entries, 2 n // batch batches per epoch.
+
+    subset (sample indices; None = all, the index and flag streams of a seed then being what they were): training
+    draws from these samples only (the rest are held out, onitama_az.holdout): a batch is
+    subset[choose_batches(rng, len(subset), ...)], an epoch len(subset) // batch batches, and mode 2 draws from
+    2 len(subset) virtual entries."""
     trainer.load_samples(samples)
-    return _epochs(trainer, len(samples), epochs, batch, seed, reflect)
+    return _epochs(trainer, len(samples), epochs, batch, seed, reflect, subset)
 
 
 def train_epochs_device(trainer: Trainer, ptr: int, n: int, epochs: int = 10, batch: int = 512, seed: int = 0,
-                        reflect: int = 0) -> List[EpochLoss]:
+                        reflect: int = 0, subset: Optional[np.ndarray] = None) -> List[EpochLoss]:
     """train_epochs on n records that are already in device memory at `ptr` (a ReplayBuffer view; the trainer's
     device): they are bound (oaz_trainer_bind_device_samples), never copied, and the index and flag streams are
     those train_epochs draws for the same n, seed and reflect. The memory stays the caller's and stays as it is
     until the call returns."""
     trainer.bind_device_samples(ptr, n)
-    return _epochs(trainer, int(n), epochs, batch, seed, reflect)
+    return _epochs(trainer, int(n), epochs, batch, seed, reflect, subset)
 
 
-def _epochs(trainer, n_samples: int, epochs: int, batch: int, seed: int, reflect: int) -> List[EpochLoss]:
+def _epochs(trainer, n_samples: int, epochs: int, batch: int, seed: int, reflect: int,
+            subset: Optional[np.ndarray] = None) -> List[EpochLoss]:
     """The epochs of train_epochs on the samples the trainer holds."""
+    subset, n_samples = _subset(subset, n_samples)
     rng = np.random.default_rng(seed)
     flag_rng = np.random.default_rng([REFLECT_TAG, seed])
     out: List[EpochLoss] = []
     for _ in range(epochs):
         if n_samples < batch:
             break
-        idx, flags = epoch_batches(rng, flag_rng, n_samples, batch, reflect)
+        idx, flags = epoch_batches(rng, flag_rng, n_samples, batch, reflect, subset=subset)
         n = len(idx)
         _set_batches(trainer, idx, flags)
         trainer.train(0, n)
@@ -253,7 +356,7 @@ def _allreduce_sum(t, comm, stream: int) -> None:
 
 
 def train_epochs_dp(trainer: Trainer, samples: np.ndarray, epochs: int, batch: int, seed: int, rank: int,
-                    world: int, comm=None, reflect: int = 0) -> List[EpochLoss]:
+                    world: int, comm=None, reflect: int = 0, subset: Optional[np.ndarray] = None) -> List[EpochLoss]:
     """Data-parallel epochs (train.rs:264-325 over `world` GPUs): the global batch `batch` is split
     into `world` shards of batch/world samples; the gradient buffer is summed over ranks (RCCL via
     `comm`, an onitama_az.dist.Comm) and applied with grad_scale 1/world, so every rank takes the
@@ -261,20 +364,22 @@ def train_epochs_dp(trainer: Trainer, samples: np.ndarray, epochs: int, batch: i
     their shard. BN batch statistics are per shard (DDP without SyncBatchNorm); the running
     statistics are averaged over ranks after each epoch, and the reported losses are the global
     ones, so every rank ends each epoch with identical weights and statistics. reflect: as train_epochs; every
-    rank draws the same flags and takes the column slice of them that it takes of the indices."""
+    rank draws the same flags and takes the column slice of them that it takes of the indices. subset: as
+    train_epochs, the same on every rank."""
     return _dp(trainer, lambda: trainer.load_samples(samples), len(samples), epochs, batch, seed, rank, world, comm,
-               reflect)
+               reflect, subset)
 
 
 def train_epochs_dp_device(trainer: Trainer, ptr: int, n: int, epochs: int, batch: int, seed: int, rank: int,
-                           world: int, comm=None, reflect: int = 0) -> List[EpochLoss]:
+                           world: int, comm=None, reflect: int = 0,
+                           subset: Optional[np.ndarray] = None) -> List[EpochLoss]:
     """train_epochs_dp on n records bound in device memory (train_epochs_device's terms): every rank binds its own
     copy of the same records."""
     return _dp(trainer, lambda: trainer.bind_device_samples(ptr, n), int(n), epochs, batch, seed, rank, world, comm,
-               reflect)
+               reflect, subset)
 
 
-def _dp(trainer, attach, n_samples, epochs, batch, seed, rank, world, comm, reflect) -> List[EpochLoss]:
+def _dp(trainer, attach, n_samples, epochs, batch, seed, rank, world, comm, reflect, subset=None) -> List[EpochLoss]:
     import torch
     assert batch % world == 0 and (batch // world) % 16 == 0
     shard = batch // world
@@ -284,16 +389,17 @@ def _dp(trainer, attach, n_samples, epochs, batch, seed, rank, world, comm, refl
     ts = torch.cuda.Stream()
     with torch.cuda.stream(ts):
         out = _epochs_dp(trainer, attach, n_samples, epochs, batch, seed, rank, world, comm, shard, ts.cuda_stream,
-                         reflect)
+                         reflect, subset)
     trainer.sync()
     trainer.set_stream(None)
     return out
 
 
 def _epochs_dp(trainer, attach, n_samples, epochs, batch, seed, rank, world, comm, shard, stream,
-               reflect=0) -> List[EpochLoss]:
+               reflect=0, subset=None) -> List[EpochLoss]:
     """attach(): makes the n_samples records the trainer's (load_samples or bind_device_samples)."""
     import torch
+    subset, n_samples = _subset(subset, n_samples)
     trainer.set_stream(stream)
     dev = f"cuda:{torch.cuda.current_device()}"
     ptr, n = trainer.grads_device()
@@ -307,7 +413,7 @@ def _epochs_dp(trainer, attach, n_samples, epochs, batch, seed, rank, world, com
     for _ in range(epochs):
         if n_samples < batch:
             break
-        idx, flags = epoch_batches(rng, flag_rng, n_samples, batch, reflect, rank, world)
+        idx, flags = epoch_batches(rng, flag_rng, n_samples, batch, reflect, rank, world, subset)
         nb = len(idx)
         assert idx.shape[1] == shard
         _set_batches(trainer, idx, flags)
